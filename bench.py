@@ -2,6 +2,12 @@
 """Benchmark: fast_consensus() hot path on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config lfr1m|lfr100k|lfr100k_lpm|lfr1k|sbm4m]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the result line.  --full adds the CPU
+baseline (`cpu_baseline`, null otherwise).  --dump-outputs DIR writes the last timed step's
+labelings (a fixed node sample) and stats as DIR/*.npy: the same arguments give the same graph
+and engine seeds, so two builds can be compared output for output.
 
 One step = one whole fast_consensus(G, algorithm, n_p, tau, delta) call as §8(d) metric (1)
 defines it: graph upload from host arrays (PCIe + device ingest + CSR build) -> every
@@ -211,6 +217,28 @@ def load_lv_traffic(config, kernel):
         "no %s counters in %s" % (kernel, os.path.basename(p))
 
 
+# ------------------------------------------------------------------------------- output dump
+DUMP_STATS = ("iterations", "exit_check", "hit_iter_cap", "n_p", "m_final", "partition_edges")
+DUMP_LABEL_BYTES = 48 << 20     # the labels sample (float32); everything written stays under 64 MB
+DUMP_SAMPLE_SEED = 20190417
+
+
+def dump_outputs(path, labels, st):
+    """--dump-outputs: what the last timed step handed its caller, as <path>/<name>.npy.
+    labels.npy: the n_p final labelings (float32 when every label is exact in it, else float64)
+    at a fixed, seeded sample of nodes -- all of them when they fit; labels_nodes.npy: the
+    sampled node ids, ascending (float64); stats.npy: DUMP_STATS of the step's stats (float64)."""
+    n_p, n = labels.shape
+    k = min(n, max(1, DUMP_LABEL_BYTES // (8 * n_p)))
+    nodes = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+    sample = np.ascontiguousarray(labels[:, nodes])
+    dt = np.float32 if np.abs(sample).max(initial=0) <= (1 << 24) else np.float64
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "labels.npy"), sample.astype(dt))
+    np.save(os.path.join(path, "labels_nodes.npy"), nodes.astype(np.float64))
+    np.save(os.path.join(path, "stats.npy"), np.array([st.get(k, 0) for k in DUMP_STATS], np.float64))
+
+
 # ------------------------------------------------------------------------------- launcher
 def _free_port():
     s = socket.socket()
@@ -238,7 +266,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="lfr1m", choices=sorted(CONFIGS))
     ap.add_argument("--seed", type=int, default=42)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the CPU baseline (the reference-semantics port on the host cores: tens of "
+                         "seconds at the default config); a plain run times the GPU steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned as DIR/<name>.npy "
+                         "(labels: a fixed sample of nodes, every replica; stats)")
     ap.add_argument("--buckets", type=int, default=0)
     ap.add_argument("--chunk", type=int, default=-1, help="CD visit-order chunk (engine option; -1 = default)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (RCCL) in production; gloo to rehearse N>1 on one GPU")
@@ -260,6 +294,8 @@ def main():
                     help="TEST HOOK (launcher tests on CPU): the oracle-backed CPU model of the engine "
                          "replaces the HIP engine; the line is marked and carries no throughput claim")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = dict(CONFIGS[args.config])
     if args.n_p > 0:
         cfg["n_p"] = args.n_p
@@ -490,8 +526,12 @@ def main():
                                                     "rl_decide_ms", "lv_decide_ms", "lv_heavy_ms")}
 
     if rank == 0:
+        if args.dump_outputs:
+            # host_out holds the last timed step's labelings (every rank's rows: the barrier above)
+            dump_outputs(args.dump_outputs, host_out, st)
+            log("[rank 0] outputs of step %d written to %s" % (args.steps - 1, args.dump_outputs))
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and not model:
+        if args.full and world == 1 and not args.no_cpu_baseline and not model:
             t = time.perf_counter()
             cpu = cpu_baseline(n, u, v, cfg, args.seed)
             log("[rank 0] cpu baseline %.3g %s in %.1fs" % (cpu["value"], cpu["unit"], time.perf_counter() - t))

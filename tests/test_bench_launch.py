@@ -51,6 +51,50 @@ def test_gpus_world_size_mismatch_exits_nonzero():
     assert "mislabelled" in p.stderr
 
 
+def test_dump_outputs_repeatable_and_steps_honoured(tmp_path):
+    """--dump-outputs writes the last timed step's labelings and stats as float .npy, two runs
+    with the same arguments write the same arrays, --steps sets the number of timed steps, and a
+    plain line carries ms_per_step and no CPU baseline."""
+    lines = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, BENCH, "--engine-model", "--config", "lfr1k", "--steps", "2",
+                            "--warmup", "1", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True,
+                           cwd=ROOT, timeout=600,
+                           env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
+        lines.append(_line(p))
+    one = lines[0]
+    assert one["steps"] == 2 and len(one["per_step"]) == 2 and one["warmup"] == 1
+    assert one["ms_per_step"] > 0 and one["cpu_baseline"] is None
+    assert sorted(os.listdir(tmp_path / "a")) == ["labels.npy", "labels_nodes.npy", "stats.npy"]
+    total = 0
+    for name in os.listdir(tmp_path / "a"):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    lab, st = np.load(tmp_path / "a" / "labels.npy"), np.load(tmp_path / "a" / "stats.npy")
+    assert lab.shape == (20, 1000) and np.array_equal(lab, np.round(lab)) and lab.min() >= 0
+    assert len(np.unique(lab[0])) > 1
+    # stats of the LAST timed step
+    assert st[0] == one["config"]["iterations"][-1] and st[4] == one["config"]["m_final"][-1]
+    assert st[5] == one["per_step"][-1]["partition_edges"]
+
+
+def test_dump_outputs_samples_large_labelings(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LABEL_BYTES", 8 * 4 * 100)
+    labels = np.arange(4 * 1000, dtype=np.int32).reshape(4, 1000) + (1 << 24)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), labels, {"iterations": 2, "m_final": 7})
+    nodes = np.load(tmp_path / "a" / "labels_nodes.npy")
+    assert np.array_equal(nodes, np.load(tmp_path / "b" / "labels_nodes.npy"))
+    assert nodes.shape == (100,) and np.all(np.diff(nodes) > 0) and 0 <= nodes[0] and nodes[-1] < 1000
+    lab = np.load(tmp_path / "a" / "labels.npy")
+    assert lab.dtype == np.float64 and np.array_equal(lab, labels[:, nodes.astype(np.int64)])   # past 2^24: float64
+    assert np.load(tmp_path / "a" / "stats.npy").tolist() == [2, 0, 0, 0, 7, 0]
+
+
 def test_cpu_baseline_full_iteration_small():
     """The CPU baseline times one FULL consensus iteration (CD + consensus + threshold +
     closure + repair) of the reference-semantics port and reports cores and CPU model."""

@@ -26,7 +26,7 @@ run() {  # run <name> <timeout> <args...>
 for n in $NAMES; do
     case $n in
         suite) suite ;;
-        lfr1m) run lfr1m 400 ;;
+        lfr1m) run lfr1m 400 --full ;;
         lfr100k) run lfr100k 200 --config lfr100k --steps 5 --warmup 2 --no-cpu-baseline ;;
         lfr100k_lpm) run lfr100k_lpm 200 --config lfr100k_lpm --steps 5 --warmup 2 --no-cpu-baseline ;;
         np8) run np8 200 --n-p 8 --steps 5 --warmup 2 --no-cpu-baseline ;;
