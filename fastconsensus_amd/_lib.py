@@ -30,7 +30,10 @@ SYMBOLS = [
     "fc_closure_sample", "fc_closure_set_pairs", "fc_closure_begin", "fc_closure_block_sample",
     "fc_closure_block_add", "fc_closure_finish", "fc_closure_partial", "fc_closure_apply",
     "fc_generate_lfr", "fc_generate_sbm", "fc_read_edgelist",
+    "fc_score_set_reference", "fc_score_partitions", "fc_score_pairs",
 ]
+FC_SCORE_REF = -1
+SCORE_GRAPHS = {"input": 0, "working": 1}
 
 
 class FastConsensusError(RuntimeError):
@@ -54,6 +57,24 @@ class Stats(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class PartScore(ctypes.Structure):
+    """fc_part_score"""
+    _fields_ = [
+        ("k", ctypes.c_int64), ("max_size", ctypes.c_int64), ("sum_sq", ctypes.c_int64),
+        ("in_weight", ctypes.c_int64), ("tot_sq_lo", ctypes.c_uint64), ("tot_sq_hi", ctypes.c_uint64),
+        ("s_log", ctypes.c_double), ("entropy", ctypes.c_double), ("modularity", ctypes.c_double),
+    ]
+
+
+class PairScore(ctypes.Structure):
+    """fc_pair_score"""
+    _fields_ = [
+        ("a", ctypes.c_int32), ("b", ctypes.c_int32), ("cells", ctypes.c_int64), ("sum_sq", ctypes.c_int64),
+        ("slow_members", ctypes.c_int64), ("s_log", ctypes.c_double), ("mi", ctypes.c_double),
+        ("nmi", ctypes.c_double), ("ari", ctypes.c_double),
+    ]
 
 
 _lib = None
@@ -109,6 +130,9 @@ def load():
     L.fc_generate_lfr.argtypes = [i64, dbl, dbl, dbl, dbl, i32, i32, i32, u64, i64, vp, vp, P(i64), vp]
     L.fc_generate_sbm.argtypes = [i64, i32, dbl, dbl, u64, i64, vp, vp, P(i64)]
     L.fc_read_edgelist.argtypes = [ctypes.c_char_p, P(i64), P(i64), vp, vp, vp]
+    L.fc_score_set_reference.argtypes = [vp, vp]
+    L.fc_score_partitions.argtypes = [vp, c_int, vp]       # fc_part_score[n_r]
+    L.fc_score_pairs.argtypes = [vp, vp, P(i64), vp]       # int32[npairs][2] or NULL, fc_pair_score[]
     _lib = L
     return L
 

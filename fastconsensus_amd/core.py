@@ -300,6 +300,110 @@ class Engine:
                                        int(iteration), ctypes.byref(conv), ctypes.byref(m)))
         return bool(conv.value), m.value
 
+    # -- scoring the local labelings (fc_score_*) ---------------------------------------
+    def set_reference(self, labels):
+        """Install a reference labeling [n] (node order) for score_pairs' FC_SCORE_REF index; ids
+        outside [0, n) are compacted as set_labels does.  None clears it (so does load_graph)."""
+        if labels is None:
+            check(self._L.fc_score_set_reference(self._ctx, None))
+            return
+        labels = np.asarray(labels)
+        if labels.shape != (self.n,):
+            raise ValueError("the reference labeling must have shape (%d,)" % self.n)
+        if labels.size and (not np.issubdtype(labels.dtype, np.integer) or labels.min() < 0
+                            or labels.max() >= self.n):
+            labels = np.unique(labels, return_inverse=True)[1].reshape(-1)   # any ids (strings too): equality only
+        labels = np.ascontiguousarray(labels, dtype=np.int32)
+        check(self._L.fc_score_set_reference(self._ctx, ptr(labels)))
+
+    def score_partitions(self, graph="input"):
+        """Per local replica on `graph` ("input": the loaded G with unit weights, "working": the
+        working graph with its consensus weights): a dict of numpy arrays [n_r] -- k, max_size,
+        sum_sq, in_weight (int64), tot_sq (exact Python ints, dtype object), s_log, entropy,
+        modularity (float64)."""
+        if graph not in _lib.SCORE_GRAPHS:
+            raise ValueError("graph must be one of %s" % (sorted(_lib.SCORE_GRAPHS),))
+        n_r = self.replica_info()[0]
+        rec = np.zeros(max(n_r, 1), dtype=PART_DTYPE)
+        check(self._L.fc_score_partitions(self._ctx, _lib.SCORE_GRAPHS[graph], ptr(rec)))
+        rec = rec[:n_r]
+        out = {k: rec[k].copy() for k in ("k", "max_size", "sum_sq", "in_weight", "s_log", "entropy", "modularity")}
+        out["tot_sq"] = np.array([(int(h) << 64) | int(l) for l, h in zip(rec["tot_sq_lo"], rec["tot_sq_hi"])],
+                                 dtype=object)
+        return out
+
+    def score_pairs(self, pairs=None):
+        """Contingency scores of ordered pairs (a, b) of local replica indices (-1: the
+        reference labeling): a structured array with fields a, b, cells, sum_sq, slow_members,
+        s_log, mi, nmi, ari.  pairs=None: every a < b, then (-1, b) for every b when a
+        reference is set."""
+        n_r = self.replica_info()[0]
+        if pairs is None:
+            cap = n_r * (n_r - 1) // 2 + n_r
+            parr = None
+        else:
+            parr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+            cap = len(parr)
+        rec = np.zeros(max(cap, 1), dtype=PAIR_DTYPE)
+        k = ctypes.c_int64(cap)
+        check(self._L.fc_score_pairs(self._ctx, ptr(parr), ctypes.byref(k), ptr(rec)))
+        return rec[:k.value]
+
+    def nmi_matrix(self):
+        """Symmetric [n_r, n_r] float64 NMI between the local replicas (unit diagonal)."""
+        return self._pair_matrices()[0]
+
+    def _pair_matrices(self):
+        n_r = self.replica_info()[0]
+        iu = np.triu_indices(n_r, 1)
+        rec = self.score_pairs(np.stack(iu, 1)) if n_r > 1 else np.zeros(0, PAIR_DTYPE)
+        out = []
+        for f in ("nmi", "ari"):
+            mat = np.eye(n_r, dtype=np.float64)
+            mat[iu] = rec[f]
+            mat.T[iu] = rec[f]
+            out.append(mat)
+        return out
+
+
+PART_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.PartScore._fields_], align=True)
+PAIR_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.PairScore._fields_], align=True)
+assert PART_DTYPE.itemsize == ctypes.sizeof(_lib.PartScore) and PAIR_DTYPE.itemsize == ctypes.sizeof(_lib.PairScore)
+
+
+def run_scores(eng, truth=None):
+    """The `scores` dict of fast_consensus(scores=True) from the engine's local labelings:
+    modularity and k per partition (on the input graph), the pairwise nmi / ari matrices, their
+    mean off-diagonal NMI, the medoid (largest mean NMI to the others, ties to the lowest index)
+    and, with `truth` [n] in node order, nmi_truth / ari_truth."""
+    n_p = eng.replica_info()[0]
+    part = eng.score_partitions("input")
+    nmi, ari = eng._pair_matrices()
+    out = {"modularity": part["modularity"], "k": part["k"], "nmi": nmi, "ari": ari}
+    if n_p > 1:
+        others = (nmi.sum(1) - 1.0) / (n_p - 1)
+        out["mean_pairwise_nmi"] = float(nmi[np.triu_indices(n_p, 1)].mean())
+    else:
+        others = np.ones(n_p)
+        out["mean_pairwise_nmi"] = 1.0
+    out["medoid"] = int(np.argmax(others))     # argmax returns the first of equal maxima
+    if truth is not None:
+        eng.set_reference(truth)
+        rec = eng.score_pairs(np.stack([np.full(n_p, _lib.FC_SCORE_REF), np.arange(n_p)], 1))
+        out["nmi_truth"] = rec["nmi"].copy()
+        out["ari_truth"] = rec["ari"].copy()
+    return out
+
+
+def truth_array(truth, labels):
+    """truth as an array in `labels` (node) order: a {node: community} dict or such an array."""
+    if isinstance(truth, dict):
+        return np.asarray([truth[x] for x in labels.tolist()])
+    truth = np.asarray(truth)
+    if truth.shape != (len(labels),):
+        raise ValueError("truth must be a {node: community} dict or an array of %d ids in node order" % len(labels))
+    return truth
+
 
 # ------------------------------------------------------------------------------------ inputs
 ADJ_PARALLEL_MIN = 4_000_000     # adjacency entries from which read_adjacency forks workers
@@ -565,7 +669,7 @@ def relabel_for(algorithm):
 
 
 def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, seed=None, device=0,
-                   return_stats=False, rule="fast_consensus"):
+                   return_stats=False, rule="fast_consensus", scores=False, truth=None):
     """Drop-in for fast_consensus.py:129 ``fast_consensus(G, algorithm, n_p, thresh, delta)``.
 
     G: an undirected networkx Graph (weights are ignored: the reference resets them to 1,
@@ -575,6 +679,13 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     ``break``s and returns None, :380-381).  ``seed`` makes the run reproducible (the
     reference is unseeded).  ``rule="new_consensus"`` (louvain only) switches to the
     new_consensus.py fork's weight rule (:155-163).
+
+    ``scores=True`` also scores the partitions on the device before they are converted and
+    returns ``(partitions, scores)`` -- ``(partitions, stats, scores)`` with ``return_stats`` --
+    where ``scores`` holds ``modularity[n_p]`` and ``k[n_p]`` (on G), the ``nmi[n_p, n_p]`` and
+    ``ari[n_p, n_p]`` matrices, ``mean_pairwise_nmi``, ``medoid`` (the partition with the largest
+    mean NMI to the others, ties to the lowest index) and, with ``truth`` (a ``{node: community}``
+    dict or an array in node order), ``nmi_truth[n_p]`` and ``ari_truth[n_p]``.
     """
     algo = algo_id(algorithm)
     if algo is None:
@@ -597,8 +708,10 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
         eng.set_option("relabel", relabel_for(algo))
         eng.load_graph(g.n, g.u, g.v)
         labels, stats = eng.run(algo, int(n_p), float(thresh), float(delta))
+        sc = run_scores(eng, None if truth is None else truth_array(truth, g.labels)) if scores else None
     out = labels_to_output(algorithm, g.labels, labels)
-    return (out, stats) if return_stats else out
+    res = (out,) + ((stats,) if return_stats else ()) + ((sc,) if scores else ())
+    return res if len(res) > 1 else out
 
 
 def check_consensus_graph(G, n_p, delta):

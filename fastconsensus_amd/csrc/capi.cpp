@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "fc_ctx.h"
 
@@ -153,7 +154,8 @@ void fc_destroy(fc_ctx* ctx) {
                       &c.cage, &c.deg_next, &c.iso, &c.isoflag, &c.target, &c.tw, &c.active, &c.active2,
                       &c.hit, &c.mkey, &c.mkey2, &c.midx, &c.midx2, &c.sort_tmp, &c.nodetmp, &c.nodetmp2,
                       &c.nodetmp3, &c.part, &c.ccount, &c.tailbuf, &c.tailmark, &c.sigma, &c.npos, &c.spos, &c.sinv, &c.tpos, &c.snpos, &c.st_u, &c.st_v, &c.st_w, &c.st_age,
-                      &c.st_lab, &c.clo_rec, &c.clo_hkey, &c.clo_hval, &c.clo_list, &c.clo_cnt, &c.clo_akey, &c.clo_aval, &c.clo_rowptr, &c.clo_col, &c.clo_rowptr2, &c.clo_col2, &c.clo_nrow, &c.clo_ncol, &c.clo_own, &c.clo_own2, &c.mvf};
+                      &c.st_lab, &c.clo_rec, &c.clo_hkey, &c.clo_hval, &c.clo_list, &c.clo_cnt, &c.clo_akey, &c.clo_aval, &c.clo_rowptr, &c.clo_col, &c.clo_rowptr2, &c.clo_col2, &c.clo_nrow, &c.clo_ncol, &c.clo_own, &c.clo_own2, &c.mvf,
+                      &c.sc_ref, &c.sc_key, &c.sc_val, &c.sc_ulab, &c.sc_cnt, &c.sc_nruns, &c.sc_seg, &c.sc_kd, &c.sc_kp, &c.sc_part, &c.sc_part2, &c.sc_res, &c.sc_want, &c.sc_ovf, &c.sc_e1, &c.sc_e2, &c.sc_fk1, &c.sc_fk2, &c.sc_fcnt, &c.sc_rng};
     for (auto* b : bufs) b->release();
     for (auto e : c.timer.pool) (void)hipEventDestroy(e);
     for (auto e : c.sweep_ev) (void)hipEventDestroy(e);
@@ -228,6 +230,7 @@ int fc_load_graph(fc_ctx* ctx, int64_t n, int64_t m, const int32_t* u, const int
     FC_REQUIRE(m == 0 || (u && v), FC_EINVAL, "null edge arrays");
     graph_load(c, n, m, u, v);
     c.n_r = 0;
+    c.sc_ref_set = false;   // a reference labeling belongs to the graph it was set on
     FC_API_END
 }
 
@@ -434,6 +437,64 @@ int fc_closure_apply(fc_ctx* ctx, int algo, int n_p, double delta, const void* d
     const int64_t unc = count_unconverged(c, c.g.ew.as<int32_t>(), c.g.m, n_p);
     if (converged) *converged = !((double)unc > delta * (double)c.g.m);
     if (m_out) *m_out = c.g.m;
+    FC_API_END
+}
+
+int fc_score_set_reference(fc_ctx* ctx, const int32_t* labels) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    const uint32_t lim = (uint32_t)c.N;
+    if (labels)
+        for (int64_t i = 0; i < c.N; ++i)
+            FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
+                       "reference label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    score_set_reference(c, labels);
+    FC_API_END
+}
+
+int fc_score_partitions(fc_ctx* ctx, int graph, fc_part_score* out) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings");
+    FC_REQUIRE(graph == FC_SCORE_GRAPH_INPUT || graph == FC_SCORE_GRAPH_WORKING, FC_EINVAL,
+               "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    FC_REQUIRE(out, FC_EINVAL, "null output buffer");
+    score_partitions(c, graph, out);
+    FC_API_END
+}
+
+int fc_score_pairs(fc_ctx* ctx, const int32_t* pairs, int64_t* npairs, fc_pair_score* out) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings");
+    FC_REQUIRE(npairs, FC_EINVAL, "null npairs");
+    std::vector<int32_t> all;
+    int64_t np = *npairs;
+    if (!pairs) {   // every a < b among the local replicas, plus (REF, b) when a reference is set
+        for (int a = 0; a < c.n_r; ++a)
+            for (int b = a + 1; b < c.n_r; ++b) { all.push_back(a); all.push_back(b); }
+        if (c.sc_ref_set)
+            for (int b = 0; b < c.n_r; ++b) { all.push_back(FC_SCORE_REF); all.push_back(b); }
+        np = (int64_t)all.size() / 2;
+        FC_REQUIRE(*npairs >= np, FC_EINVAL,
+                   "output holds " + std::to_string(*npairs) + " pairs; " + std::to_string(np) + " needed");
+        pairs = all.data();
+    } else {
+        FC_REQUIRE(np >= 0, FC_EINVAL, "negative pair count");
+        for (int64_t i = 0; i < 2 * np; ++i) {
+            FC_REQUIRE(pairs[i] == FC_SCORE_REF || (pairs[i] >= 0 && pairs[i] < c.n_r), FC_EINVAL,
+                       "pair index " + std::to_string(pairs[i]) + " outside the " + std::to_string(c.n_r) +
+                           " local replicas");
+            FC_REQUIRE(pairs[i] != FC_SCORE_REF || c.sc_ref_set, FC_ESTATE,
+                       "FC_SCORE_REF used with no reference set (fc_score_set_reference)");
+        }
+    }
+    FC_REQUIRE(out || np == 0, FC_EINVAL, "null output buffer");
+    if (np > 0) score_pairs(c, pairs, np, out);
+    *npairs = np;
     FC_API_END
 }
 

@@ -897,3 +897,5 @@ void closure_apply(Ctx& c, int algo, int n_p, const int32_t* counts, int iterati
 }
 
 }  // namespace fc
+
+#include "score.h"   // partition scoring (fc_score_*): its kernels use the helpers above

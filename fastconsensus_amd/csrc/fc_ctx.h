@@ -234,6 +234,17 @@ struct Ctx {
     // (FC_RL_SPLIT; other layouts run 3)
     int rl_groups_louv = getenv("FC_RL_GROUPS_LOUV") ? atoi(getenv("FC_RL_GROUPS_LOUV")) : 2;
     int rl_groups_lpa = getenv("FC_RL_GROUPS_LPA") ? atoi(getenv("FC_RL_GROUPS_LPA")) : 2;
+    // partition scoring (score.h): the reference labeling in slot order, one row's sort / segment
+    // buffers (reused row after row), per-block partials, fallback masks, offsets and key chunks
+    DevBuf sc_ref, sc_key, sc_val, sc_ulab, sc_cnt, sc_nruns, sc_seg, sc_kd, sc_kp, sc_part, sc_part2, sc_res, sc_want,
+        sc_ovf, sc_e1, sc_e2, sc_fk1, sc_fk2, sc_fcnt, sc_rng;
+    bool sc_ref_set = false;
+    // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
+    int score_slow = getenv("FC_SCORE_SLOW") ? atoi(getenv("FC_SCORE_SLOW")) : 0;
+    // longest community one wave streams; longer ones go to the fallback
+    int score_lcap = getenv("FC_SCORE_LCAP") ? atoi(getenv("FC_SCORE_LCAP")) : 16384;
+    // fallback keys per chunk (at least 2 N: an item is up to N keys); 28 bytes of scratch per key
+    int64_t score_chunk = getenv("FC_SCORE_CHUNK") ? atoll(getenv("FC_SCORE_CHUNK")) : (int64_t)1 << 22;
 };
 
 struct Ctx;
@@ -316,6 +327,10 @@ void closure_from_pairs(Ctx& c, int64_t npairs, const int32_t* pairs, int iterat
 void closure_partial(Ctx& c, int32_t* out);
 void closure_apply(Ctx& c, int algo, int n_p, const int32_t* counts, int iteration);
 int64_t count_unconverged(Ctx& c, const int32_t* w, int64_t m, int n_p);
+// score.h (in consensus.hip): labels in node order or null; out[n_r]; pairs validated by the caller
+void score_set_reference(Ctx& c, const int32_t* labels);
+void score_partitions(Ctx& c, int graph, fc_part_score* out);
+void score_pairs(Ctx& c, const int32_t* pairs, int64_t npairs, fc_pair_score* out);
 // timing helpers
 int timer_begin(Ctx& c);
 void timer_end(Ctx& c, int slot, int begin_ev);

@@ -260,6 +260,46 @@ int fc_closure_partial(fc_ctx* ctx, void* dev_out);
 int fc_closure_apply(fc_ctx* ctx, int algo, int n_p, double delta, const void* dev_counts,
                      int iteration, int* converged, int64_t* m_out);
 
+/* ---- scoring the local labelings (those left by fc_run, fc_cd or fc_set_labels) ------- */
+/* Read-only for everything a later call can observe; all work on the context's stream; local to
+ * a rank.  n = nodes, ln = natural logarithm. */
+#define FC_SCORE_REF (-1)          /* pair index of the reference labeling */
+#define FC_SCORE_GRAPH_INPUT 0     /* the loaded G, unit weights */
+#define FC_SCORE_GRAPH_WORKING 1   /* the working graph with its consensus weights */
+typedef struct fc_part_score {
+    int64_t k;            /* communities */
+    int64_t max_size;     /* size of the largest */
+    int64_t sum_sq;       /* sum_c size_c^2 */
+    int64_t in_weight;    /* sum of w_uv over edges inside a community, each edge once */
+    uint64_t tot_sq_lo;   /* sum_c (sum_{v in c} weighted degree_v)^2, exact, 128 bits */
+    uint64_t tot_sq_hi;
+    double s_log;         /* sum_c size_c ln size_c */
+    double entropy;       /* ln n - s_log / n */
+    double modularity;    /* 2 in_weight / W2 - tot_sq / W2^2, W2 = total weighted degree; 0 if W2 = 0 */
+} fc_part_score;
+typedef struct fc_pair_score {
+    int32_t a, b;         /* local replica indices, or FC_SCORE_REF */
+    int64_t cells;        /* nonzero cells n_ij of the contingency table */
+    int64_t sum_sq;       /* sum n_ij^2 */
+    int64_t slow_members; /* vertices of this pair the exact fallback handled (diagnostic) */
+    double s_log;         /* sum n_ij ln n_ij */
+    double mi;            /* ln n + (s_log_ab - s_log_a - s_log_b) / n, clamped at 0 */
+    double nmi;           /* mi / ((H_a + H_b) / 2) (sklearn's arithmetic normalisation); 1 when both
+                             have one community, else 0 when mi <= 0 */
+    double ari;           /* adjusted Rand index from the integer sums; 1 when its denominator is 0 */
+} fc_pair_score;
+/* Reference labeling [n] in node order, ids in [0, n) (FC_EINVAL otherwise); NULL clears it, and
+ * so does fc_load_graph. */
+int fc_score_set_reference(fc_ctx* ctx, const int32_t* labels);
+/* out[count] (fc_replica_info): one record per local replica on the chosen graph. */
+int fc_score_partitions(fc_ctx* ctx, int graph, fc_part_score* out);
+/* pairs: int32[npairs][2]; NULL = every a < b among the local replicas, then (FC_SCORE_REF, b) for
+ * every b if a reference is set.  *npairs in: the pair count (pairs given) or the capacity of out
+ * (pairs NULL); out: records written.  FC_EINVAL (nothing written) for an index out of range or a
+ * capacity too small, FC_ESTATE without labelings or for FC_SCORE_REF with no reference.
+ * fc_score_partitions and fc_score_pairs return FC_ELIMIT with more than 2048 local replicas. */
+int fc_score_pairs(fc_ctx* ctx, const int32_t* pairs, int64_t* npairs, fc_pair_score* out);
+
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
  * Writes at most m_cap edges into u/v and the planted community of every node. */
