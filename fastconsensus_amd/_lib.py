@@ -31,6 +31,7 @@ SYMBOLS = [
     "fc_closure_block_add", "fc_closure_finish", "fc_closure_partial", "fc_closure_apply",
     "fc_generate_lfr", "fc_generate_sbm", "fc_read_edgelist",
     "fc_score_set_reference", "fc_score_partitions", "fc_score_pairs",
+    "fc_consensus_support", "fc_consensus_partition", "fc_consensus_timing",
 ]
 FC_SCORE_REF = -1
 SCORE_GRAPHS = {"input": 0, "working": 1}
@@ -75,6 +76,19 @@ class PairScore(ctypes.Structure):
         ("slow_members", ctypes.c_int64), ("s_log", ctypes.c_double), ("mi", ctypes.c_double),
         ("nmi", ctypes.c_double), ("ari", ctypes.c_double),
     ]
+
+
+class ConsensusInfo(ctypes.Structure):
+    """fc_consensus_info"""
+    _fields_ = [
+        ("edges", ctypes.c_int64), ("kept_edges", ctypes.c_int64), ("unanimous_edges", ctypes.c_int64),
+        ("split_edges", ctypes.c_int64), ("k", ctypes.c_int64), ("max_size", ctypes.c_int64),
+        ("singletons", ctypes.c_int64), ("n_total", ctypes.c_int32), ("passes", ctypes.c_int32),
+        ("cut", ctypes.c_double),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 _lib = None
@@ -133,6 +147,10 @@ def load():
     L.fc_score_set_reference.argtypes = [vp, vp]
     L.fc_score_partitions.argtypes = [vp, c_int, vp]       # fc_part_score[n_r]
     L.fc_score_pairs.argtypes = [vp, vp, P(i64), vp]       # int32[npairs][2] or NULL, fc_pair_score[]
+    L.fc_consensus_support.argtypes = [vp, c_int, vp]
+    # graph, dev_support or NULL, n_total, agreement, labels, hist, node_in, node_out, fc_consensus_info
+    L.fc_consensus_partition.argtypes = [vp, c_int, vp, c_int, dbl, vp, vp, vp, vp, vp]
+    L.fc_consensus_timing.argtypes = [vp, P(dbl)]
     _lib = L
     return L
 

@@ -3,7 +3,9 @@
 Same flags, defaults, validation messages and exit status, same output tree:
 ``out_partitions_t{tau}_d{delta}_np{n_p}/1..n_p`` and ``memberships_t.../0..n_p-1``
 (louvain only; the directory is created for every algorithm).  Additive flags:
-``--seed`` (the reference is unseeded) and ``--device``.
+``--seed`` (the reference is unseeded), ``--device`` and ``--consensus THETA``, which also writes
+the consensus partition (``Engine.consensus_partition``) to ``consensus_t.../partition`` (one
+community per line) and ``consensus_t.../membership`` (``node+1<TAB>community+1``, sorted by node).
 """
 import argparse
 import os
@@ -47,6 +49,8 @@ def build_parser():
     p.add_argument('--device', type=int, default=0, help=argparse.SUPPRESS)
     # extension: the new_consensus.py fork's weight rule (:155-163), louvain only
     p.add_argument('--rule', type=str, default='fast_consensus', choices=RULES, help=argparse.SUPPRESS)
+    # extension: also write the consensus partition at this agreement threshold
+    p.add_argument('--consensus', type=float, default=None, help=argparse.SUPPRESS)
     return p
 
 
@@ -80,12 +84,32 @@ def write_outputs(args, output, root='.'):
                 print(*community, file=f)
 
 
+def write_consensus(args, node_labels, labels, root='.'):
+    """consensus_t{tau}_d{delta}_np{n_p}/partition (one community per line, like out_partitions)
+    and /membership (node+1 <TAB> community+1, sorted by node).  labels: [n] in node order."""
+    d = os.path.join(root, 'consensus_' + output_dirs(args)[0][len('out_partitions_'):])
+    os.makedirs(d, exist_ok=True)
+    nodes = list(node_labels.tolist())
+    part = {}
+    for node, c in zip(nodes, labels.tolist()):
+        part.setdefault(c, []).append(node)
+    with open(os.path.join(d, 'partition'), 'w') as f:
+        for c in sorted(part):
+            print(*part[c], file=f)
+    with open(os.path.join(d, 'membership'), 'w') as f:
+        for k, v in sorted(zip(nodes, labels.tolist())):
+            f.write(str(k + 1) + "\t" + str(v + 1) + '\n')
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.t is None:
         args.t = DEFAULT_TAU.get(args.alg, 0.2)
     if check_arguments(args) is False:
         sys.exit(0)                               # quit() -> exit status 0 (:430-432)
+    if args.consensus is not None and not 0 <= args.consensus <= 1:
+        raise SystemExit("--consensus must lie in [0, 1]")
+    cons = None
     g = IdGraph.from_edgelist_file(args.f)
     algo = algo_id(args.alg)
     if algo is None:
@@ -96,10 +120,14 @@ def main(argv=None):
         with Engine(device=args.device, seed=args.seed) as eng:
             eng.load_graph(g.n, g.u, g.v)
             labels, _ = eng.run(algo, args.np, args.t, args.d)
+            if args.consensus is not None:
+                cons = eng.consensus_partition(args.consensus)
         output = labels_to_output(args.alg, g.labels, labels)
     if output is None:                            # reference: TypeError on len(None)
         raise SystemExit("fast_consensus returned None")
     write_outputs(args, output)
+    if cons is not None:
+        write_consensus(args, g.labels, cons["labels"])
 
 
 if __name__ == "__main__":

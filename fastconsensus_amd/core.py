@@ -349,6 +349,68 @@ class Engine:
         check(self._L.fc_score_pairs(self._ctx, ptr(parr), ctypes.byref(k), ptr(rec)))
         return rec[:k.value]
 
+    # -- the consensus partition (fc_consensus_*) ----------------------------------------
+    def _graph_edges(self, graph):
+        if graph not in _lib.SCORE_GRAPHS:
+            raise ValueError("graph must be one of %s" % (sorted(_lib.SCORE_GRAPHS),))
+        _, m, m0 = self.graph_info()
+        return m0 if graph == "input" else m
+
+    def consensus_support(self, graph="input", dev_out=None):
+        """Per edge of `graph`, the number of local labelings that put both ends in one community:
+        an int32 device tensor [m] in the engine's edge order (consensus_partial's; the same on
+        every engine that loaded the graph with the same seed and options), written into
+        `dev_out` when given.  Ranks add theirs (SUM) and hand the total to consensus_partition."""
+        import torch
+        m = self._graph_edges(graph)
+        if dev_out is None:
+            dev_out = torch.empty(max(m, 1), dtype=torch.int32, device="cuda:%d" % self.device)
+        elif dev_out.dtype != torch_int32() or dev_out.numel() < m:
+            raise ValueError("dev_out must be an int32 tensor of >= %d elements" % m)
+        check(self._L.fc_consensus_support(self._ctx, _lib.SCORE_GRAPHS[graph], self._dev(dev_out)))
+        self._written()
+        return dev_out[:m]
+
+    def consensus_partition(self, agreement=0.5, graph="input", dev_support=None, n_total=None):
+        """The consensus partition: the connected components of the edges of `graph` on which at
+        least agreement * n_total labelings agree, numbered by smallest node.  `dev_support`:
+        None (the local labelings are counted, n_total = their number) or an int32 device tensor
+        [m] already summed over `n_total` replicas.  Returns a dict: labels int32[n] (node
+        order), support_hist int64[n_total + 1], node_in / node_out int64[n] (support summed over
+        a node's edges inside / leaving its consensus community), stability float64[n] =
+        node_in / (node_in + node_out) (1.0 for a node without support), and the
+        fc_consensus_info fields (edges, kept_edges, unanimous_edges, split_edges, k, max_size,
+        singletons, n_total, passes, cut)."""
+        m = self._graph_edges(graph)
+        if dev_support is None:
+            nt = self.replica_info()[0]
+        else:
+            if n_total is None:
+                raise ValueError("dev_support needs n_total, the number of replicas it was summed over")
+            if dev_support.dtype != torch_int32() or dev_support.numel() < m:
+                raise ValueError("dev_support must be an int32 tensor of >= %d elements" % m)
+            nt = int(n_total)
+        n = self.n
+        labels = np.empty(n, np.int32)
+        hist = np.zeros(max(nt, 0) + 1, np.int64)
+        nin = np.empty(n, np.int64)
+        nout = np.empty(n, np.int64)
+        info = _lib.ConsensusInfo()
+        check(self._L.fc_consensus_partition(self._ctx, _lib.SCORE_GRAPHS[graph], self._dev(dev_support), nt,
+                                             float(agreement), ptr(labels), ptr(hist), ptr(nin), ptr(nout),
+                                             ctypes.addressof(info)))
+        out = {"labels": labels, "support_hist": hist, "node_in": nin, "node_out": nout}
+        out.update(info.as_dict())
+        out["stability"] = stability(nin, nout)
+        return out
+
+    def consensus_timing(self):
+        """Device milliseconds of the phases of the last consensus_partition made with timing on
+        (set_timing): support, histogram, components, renumber (+ sizes), node_sums."""
+        ms = (ctypes.c_double * 5)()
+        check(self._L.fc_consensus_timing(self._ctx, ms))
+        return dict(zip(("support", "histogram", "components", "renumber", "node_sums"), ms))
+
     def nmi_matrix(self):
         """Symmetric [n_r, n_r] float64 NMI between the local replicas (unit diagonal)."""
         return self._pair_matrices()[0]
@@ -369,6 +431,40 @@ class Engine:
 PART_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.PartScore._fields_], align=True)
 PAIR_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.PairScore._fields_], align=True)
 assert PART_DTYPE.itemsize == ctypes.sizeof(_lib.PartScore) and PAIR_DTYPE.itemsize == ctypes.sizeof(_lib.PairScore)
+CONSENSUS_INFO_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.ConsensusInfo._fields_], align=True)
+assert CONSENSUS_INFO_DTYPE.itemsize == ctypes.sizeof(_lib.ConsensusInfo)
+
+
+def stability(node_in, node_out):
+    """node_in / (node_in + node_out) per node, 1.0 where both are 0 (a node without support)."""
+    tot = node_in + node_out
+    out = np.ones(len(tot), np.float64)
+    nz = tot != 0
+    out[nz] = node_in[nz] / tot[nz]
+    return out
+
+
+def consensus_scores(eng, sc, cons, truth=None):
+    """Adds to the `scores` dict what relates the n_p partitions to the consensus partition:
+    nmi_consensus / ari_consensus [n_p] (the consensus labeling installed as the reference), then
+    -- the engine's labelings are REPLACED by the consensus labeling as a one-replica batch, so
+    the caller has downloaded them -- consensus_modularity (on the input graph) and, with
+    `truth`, consensus_nmi_truth / consensus_ari_truth."""
+    n_p = eng.replica_info()[0]
+    eng.set_reference(cons["labels"])
+    rec = eng.score_pairs(np.stack([np.full(n_p, _lib.FC_SCORE_REF), np.arange(n_p)], 1))
+    sc["nmi_consensus"] = rec["nmi"].copy()
+    sc["ari_consensus"] = rec["ari"].copy()
+    eng.set_labels(cons["labels"][None, :])
+    sc["consensus_modularity"] = float(eng.score_partitions("input")["modularity"][0])
+    if truth is not None:
+        eng.set_reference(truth)
+        rec = eng.score_pairs([(_lib.FC_SCORE_REF, 0)])
+        sc["consensus_nmi_truth"] = float(rec["nmi"][0])
+        sc["consensus_ari_truth"] = float(rec["ari"][0])
+    else:
+        eng.set_reference(None)
+    return sc
 
 
 def run_scores(eng, truth=None):
@@ -669,7 +765,7 @@ def relabel_for(algorithm):
 
 
 def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, seed=None, device=0,
-                   return_stats=False, rule="fast_consensus", scores=False, truth=None):
+                   return_stats=False, rule="fast_consensus", scores=False, truth=None, consensus=None):
     """Drop-in for fast_consensus.py:129 ``fast_consensus(G, algorithm, n_p, thresh, delta)``.
 
     G: an undirected networkx Graph (weights are ignored: the reference resets them to 1,
@@ -686,6 +782,15 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     ``ari[n_p, n_p]`` matrices, ``mean_pairwise_nmi``, ``medoid`` (the partition with the largest
     mean NMI to the others, ties to the lowest index) and, with ``truth`` (a ``{node: community}``
     dict or an array in node order), ``nmi_truth[n_p]`` and ``ari_truth[n_p]``.
+
+    ``consensus=theta`` (a float in [0, 1]) appends a ``consensus`` dict to the returned tuple
+    (after ``stats`` and ``scores`` when present): the consensus partition of the n_p partitions
+    -- the connected components of the edges of G on which at least theta * n_p of them agree
+    (``Engine.consensus_partition``) -- with ``labels``, ``support_hist``, ``node_in``,
+    ``node_out``, ``stability``, the info fields and ``partition``, a ``{node: community}`` dict.
+    With ``scores=True`` as well, ``scores`` gains ``nmi_consensus[n_p]`` and
+    ``ari_consensus[n_p]`` (every partition against the consensus partition),
+    ``consensus_modularity`` and, with ``truth``, ``consensus_nmi_truth`` / ``consensus_ari_truth``.
     """
     algo = algo_id(algorithm)
     if algo is None:
@@ -708,9 +813,16 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
         eng.set_option("relabel", relabel_for(algo))
         eng.load_graph(g.n, g.u, g.v)
         labels, stats = eng.run(algo, int(n_p), float(thresh), float(delta))
-        sc = run_scores(eng, None if truth is None else truth_array(truth, g.labels)) if scores else None
+        tr = None if truth is None else truth_array(truth, g.labels)
+        cons = eng.consensus_partition(float(consensus)) if consensus is not None else None
+        sc = run_scores(eng, tr) if scores else None
+        if cons is not None and scores:
+            consensus_scores(eng, sc, cons, tr)
     out = labels_to_output(algorithm, g.labels, labels)
-    res = (out,) + ((stats,) if return_stats else ()) + ((sc,) if scores else ())
+    if cons is not None:
+        cons["partition"] = dict(zip(np.asarray(g.labels).tolist(), cons["labels"].tolist()))
+    res = (out,) + ((stats,) if return_stats else ()) + ((sc,) if scores else ()) + \
+        ((cons,) if cons is not None else ())
     return res if len(res) > 1 else out
 
 

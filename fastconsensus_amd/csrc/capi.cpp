@@ -155,7 +155,8 @@ void fc_destroy(fc_ctx* ctx) {
                       &c.hit, &c.mkey, &c.mkey2, &c.midx, &c.midx2, &c.sort_tmp, &c.nodetmp, &c.nodetmp2,
                       &c.nodetmp3, &c.part, &c.ccount, &c.tailbuf, &c.tailmark, &c.sigma, &c.npos, &c.spos, &c.sinv, &c.tpos, &c.snpos, &c.st_u, &c.st_v, &c.st_w, &c.st_age,
                       &c.st_lab, &c.clo_rec, &c.clo_hkey, &c.clo_hval, &c.clo_list, &c.clo_cnt, &c.clo_akey, &c.clo_aval, &c.clo_rowptr, &c.clo_col, &c.clo_rowptr2, &c.clo_col2, &c.clo_nrow, &c.clo_ncol, &c.clo_own, &c.clo_own2, &c.mvf,
-                      &c.sc_ref, &c.sc_key, &c.sc_val, &c.sc_ulab, &c.sc_cnt, &c.sc_nruns, &c.sc_seg, &c.sc_kd, &c.sc_kp, &c.sc_part, &c.sc_part2, &c.sc_res, &c.sc_want, &c.sc_ovf, &c.sc_e1, &c.sc_e2, &c.sc_fk1, &c.sc_fk2, &c.sc_fcnt, &c.sc_rng};
+                      &c.sc_ref, &c.sc_key, &c.sc_val, &c.sc_ulab, &c.sc_cnt, &c.sc_nruns, &c.sc_seg, &c.sc_kd, &c.sc_kp, &c.sc_part, &c.sc_part2, &c.sc_res, &c.sc_want, &c.sc_ovf, &c.sc_e1, &c.sc_e2, &c.sc_fk1, &c.sc_fk2, &c.sc_fcnt, &c.sc_rng,
+                      &c.cp_sup, &c.cp_parent, &c.cp_flag, &c.cp_rank, &c.cp_lab, &c.cp_labi, &c.cp_size, &c.cp_hist, &c.cp_nin, &c.cp_nout};
     for (auto* b : bufs) b->release();
     for (auto e : c.timer.pool) (void)hipEventDestroy(e);
     for (auto e : c.sweep_ev) (void)hipEventDestroy(e);
@@ -495,6 +496,43 @@ int fc_score_pairs(fc_ctx* ctx, const int32_t* pairs, int64_t* npairs, fc_pair_s
     FC_REQUIRE(out || np == 0, FC_EINVAL, "null output buffer");
     if (np > 0) score_pairs(c, pairs, np, out);
     *npairs = np;
+    FC_API_END
+}
+
+static bool score_graph_id(int graph) { return graph == FC_SCORE_GRAPH_INPUT || graph == FC_SCORE_GRAPH_WORKING; }
+
+int fc_consensus_support(fc_ctx* ctx, int graph, void* dev_out) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings: run fc_run, fc_cd or fc_set_labels first");
+    FC_REQUIRE(dev_out || (graph == FC_SCORE_GRAPH_INPUT ? c.g0.m : c.g.m) == 0, FC_EINVAL, "null output buffer");
+    consensus_support(c, graph, (int32_t*)dev_out);
+    FC_API_END
+}
+
+int fc_consensus_partition(fc_ctx* ctx, int graph, const void* dev_support, int n_total, double agreement,
+                           int32_t* labels_out, int64_t* support_hist, int64_t* node_in, int64_t* node_out,
+                           fc_consensus_info* info) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(agreement >= 0.0 && agreement <= 1.0, FC_EINVAL, "agreement must lie in [0, 1]");   // NaN fails both
+    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    FC_REQUIRE(!dev_support || n_total >= 1, FC_EINVAL, "reduced support needs n_total >= 1");
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(dev_support || c.n_r > 0, FC_ESTATE,
+               "no labelings and no support: run fc_run, fc_cd or fc_set_labels first, or pass dev_support");
+    consensus_partition(c, graph, (const int32_t*)dev_support, n_total, agreement, labels_out, support_hist, node_in,
+                        node_out, info);
+    FC_API_END
+}
+
+int fc_consensus_timing(fc_ctx* ctx, double* ms) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(ms, FC_EINVAL, "null output buffer");
+    for (int i = 0; i < CP_PHASES; ++i) ms[i] = c.cp_ms[i];
     FC_API_END
 }
 

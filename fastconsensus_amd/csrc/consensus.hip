@@ -899,3 +899,4 @@ void closure_apply(Ctx& c, int algo, int n_p, const int32_t* counts, int iterati
 }  // namespace fc
 
 #include "score.h"   // partition scoring (fc_score_*): its kernels use the helpers above
+#include "components.h"   // consensus partition (fc_consensus_support / fc_consensus_partition)

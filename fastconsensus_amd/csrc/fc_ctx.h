@@ -239,6 +239,12 @@ struct Ctx {
     DevBuf sc_ref, sc_key, sc_val, sc_ulab, sc_cnt, sc_nruns, sc_seg, sc_kd, sc_kp, sc_part, sc_part2, sc_res, sc_want,
         sc_ovf, sc_e1, sc_e2, sc_fk1, sc_fk2, sc_fcnt, sc_rng;
     bool sc_ref_set = false;
+    // consensus partition (components.h): support, union-find parents, root flags and their ranks,
+    // labels by node and by internal vertex, community sizes, support histogram, per-node sums
+    // device time of the last call's phases (timing enabled): support, histogram, components,
+    // renumber + sizes, node sums
+    double cp_ms[5] = {0, 0, 0, 0, 0};
+    DevBuf cp_sup, cp_parent, cp_flag, cp_rank, cp_lab, cp_labi, cp_size, cp_hist, cp_nin, cp_nout;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = getenv("FC_SCORE_SLOW") ? atoi(getenv("FC_SCORE_SLOW")) : 0;
     // longest community one wave streams; longer ones go to the fallback
@@ -248,6 +254,7 @@ struct Ctx {
 };
 
 struct Ctx;
+constexpr int CP_PHASES = 5;        // Ctx::cp_ms
 constexpr int FC_HPIN_I64 = 2048;   // pinned host scratch: per-sweep records (cd_rl.hip: boff | voff | n_active)
 // State the replica-lane engine hands to cd_run at the first filtered sweep of a hybrid batch
 // (FC_OPT_CD_ENGINE=2, cd_rl.hip): fill() writes it in cd.hip's layout on c.stream -- labels
@@ -331,6 +338,11 @@ int64_t count_unconverged(Ctx& c, const int32_t* w, int64_t m, int n_p);
 void score_set_reference(Ctx& c, const int32_t* labels);
 void score_partitions(Ctx& c, int graph, fc_part_score* out);
 void score_pairs(Ctx& c, const int32_t* pairs, int64_t npairs, fc_pair_score* out);
+// components.h (in consensus.hip): arguments validated by the caller
+void consensus_support(Ctx& c, int graph, int32_t* dev_out);
+void consensus_partition(Ctx& c, int graph, const int32_t* dev_support, int n_total, double agreement,
+                         int32_t* labels_out, int64_t* hist_out, int64_t* nin_out, int64_t* nout_out,
+                         fc_consensus_info* info);
 // timing helpers
 int timer_begin(Ctx& c);
 void timer_end(Ctx& c, int slot, int begin_ev);

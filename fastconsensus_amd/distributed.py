@@ -138,14 +138,34 @@ class SharedOutput:
             self.shm = None
 
 
+def _consensus(engine, theta, n_p, world, mine, device):
+    """The consensus partition of the run's n_p final partitions, replicated: every rank counts
+    the support of the input graph's edges over ITS replicas, one SUM all-reduce adds them, and
+    every rank takes the components of the agreeing edges (identical on every rank)."""
+    _, _, m0 = engine.graph_info()
+    sup = torch.zeros(max(m0, 1), dtype=torch.int32, device=device)
+    if mine > 0:
+        engine.consensus_support("input", sup)
+    _all_reduce_small(sup, dist.ReduceOp.SUM, n_p, world, 0)
+    return engine.consensus_partition(theta, "input", dev_support=sup, n_total=n_p)
+
+
+def _result(res, consensus):
+    labels, st = res
+    return (labels, st) if consensus is None else (labels, st, st.pop("consensus"))
+
+
 def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, gather=True, out=None,
-                shard_closure=False, out_shared=False):
+                shard_closure=False, out_shared=False, consensus=None):
     """Returns (labels [n_p][N] on rank 0 (None elsewhere), stats dict).  `out`: optional
     C-contiguous int32 host array [n_p][N] that rank 0 downloads into (see Engine.run).
     shard_closure: split the closure's attempts over the ranks (world > 1; same result);
     default False: every rank draws all of them (see the module docstring).
     out_shared: `out` is the same host array on every rank (SharedOutput.array): each rank
-    writes its own rows, rank 0 returns it once all have."""
+    writes its own rows, rank 0 returns it once all have.
+    consensus: an agreement threshold in [0, 1]; the return value is then (labels, stats,
+    consensus) with the dict of Engine.consensus_partition over all n_p final partitions on the
+    input graph, the same on every rank."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     if out_shared and world > 1 and out is None:
@@ -156,8 +176,8 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     louv = algo in (LOUVAIN, LOUVAIN_NC)    # louvain loop: check #1, closure counts, repair
     on_gpu = str(device).startswith("cuda")
     if not on_gpu:
-        return _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv, out,
-                     shard_closure, out_shared)
+        return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv,
+                             out, shard_closure, out_shared, consensus), consensus)
     # engine kernels and torch/RCCL ops on ONE explicit stream: no cross-stream races
     # (torch's default stream is the legacy null stream, which the engine cannot adopt)
     stream = torch.cuda.Stream(device=device)
@@ -165,15 +185,15 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     engine.set_stream(stream.cuda_stream)
     try:
         with torch.cuda.stream(stream):
-            return _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv, out,
-                         shard_closure, out_shared)
+            return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1,
+                                 louv, out, shard_closure, out_shared, consensus), consensus)
     finally:
         stream.synchronize()
         engine.set_stream(None)
 
 
 def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv, out=None,
-          shard_closure=False, out_shared=False):
+          shard_closure=False, out_shared=False, consensus=None):
     mine = r1 - r0
     engine.reset_graph()
     n, _, L = engine.graph_info()
@@ -226,6 +246,8 @@ def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank,
     st["m_final"] = m
     if mine > 0:
         engine.cd(algo, r0, mine, n_p, FINAL_PASS_ITER + it)         # final pass :383-392
+    if consensus is not None:
+        st["consensus"] = _consensus(engine, float(consensus), n_p, world, mine, device)
     if gather and world > 1 and out_shared and out is not None:
         # every rank downloads its rows into the shared host array; the barrier orders the
         # writes before rank 0 hands the array back

@@ -300,6 +300,50 @@ int fc_score_partitions(fc_ctx* ctx, int graph, fc_part_score* out);
  * fc_score_partitions and fc_score_pairs return FC_ELIMIT with more than 2048 local replicas. */
 int fc_score_pairs(fc_ctx* ctx, const int32_t* pairs, int64_t* npairs, fc_pair_score* out);
 
+/* ---- the consensus partition: components of the agreement graph ---------------------- */
+/* H = the chosen graph (FC_SCORE_GRAPH_*).  support(e) = number of labelings that put both ends
+ * of edge e in one community; e is kept iff !((double)support(e) < agreement * (double)n_total)
+ * (float64, the tau rule's form); the consensus partition is the connected components of
+ * (V, kept edges), labelled 0..k-1 by each component's smallest node id (fc_get_labels' renumber
+ * convention), so the result is unique.  Read-only for everything a later call can observe; all
+ * work on the context's stream (timed in consensus_ms). */
+typedef struct fc_consensus_info {
+    int64_t edges;            /* edges of H */
+    int64_t kept_edges;
+    int64_t unanimous_edges;  /* support == n_total */
+    int64_t split_edges;      /* support == 0 */
+    int64_t k;                /* communities of the consensus partition */
+    int64_t max_size;         /* size of the largest */
+    int64_t singletons;
+    int32_t n_total;          /* the denominator used */
+    int32_t passes;           /* launches of the hook kernel over the edge list */
+    double cut;               /* agreement * n_total as compared */
+} fc_consensus_info;
+/* support of every edge of `graph` over the local labelings into dev_out (int32[m], caller-owned),
+ * in the engine's edge order -- the order of fc_consensus_partial's output, the same on every
+ * context that loaded the same graph with the same seed and options: on FC_SCORE_GRAPH_WORKING it
+ * equals fc_consensus_partial(FC_ALGO_LPM).  Reduce with SUM across ranks.  FC_ELIMIT with more
+ * than 2048 local replicas. */
+int fc_consensus_support(fc_ctx* ctx, int graph, void* dev_out);
+/* dev_support NULL: computed from the local labelings (n_total ignored, = their count).  Otherwise
+ * int32[m] in that edge order, already reduced over n_total replicas (FC_EINVAL if a value lies
+ * outside [0, n_total]).  Any output pointer may be NULL.  labels_out int32[n] in node order;
+ * support_hist int64[n_total+1] (host); node_in[v] / node_out[v] int64[n]: the support summed over
+ * v's incident edges of H whose other end is / is not in v's consensus community.  labels_out,
+ * node_in and node_out may be host memory or device buffers of the context's GPU.
+ * FC_EINVAL: agreement outside [0, 1] or NaN, unknown graph, dev_support with n_total < 1;
+ * FC_ESTATE: no graph, or neither labelings nor dev_support; FC_ELIMIT: more than 2048 replicas.
+ * Nothing is written on error. */
+int fc_consensus_partition(fc_ctx* ctx, int graph, const void* dev_support, int n_total, double agreement,
+                           int32_t* labels_out, int64_t* support_hist, int64_t* node_in, int64_t* node_out,
+                           fc_consensus_info* info);
+
+/* Device time (ms, HIP events) of the phases of the last fc_consensus_partition made with timing
+ * enabled (fc_set_timing): ms[5] = support count, histogram, components (init + hook + flatten),
+ * renumber + sizes, node sums; a phase that did not run (support given, no node sums asked) and
+ * every phase without timing reads 0. */
+int fc_consensus_timing(fc_ctx* ctx, double* ms);
+
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
  * Writes at most m_cap edges into u/v and the planted community of every node. */
