@@ -903,8 +903,9 @@ static int tw_lpa_coarsen = 0;   /* semantics study: LPA coarse rounds up to thi
 void orc_set_lpa_coarsen(int g) { tw_lpa_coarsen = g; }
 static int tw_replica(int algo, i64 N, const i64* rowptr, const i32* col, const i32* cw, const i64* kdeg, i64 M2,
                       u64 seed, uint32_t rg, uint32_t iter, int buckets, int max_sweeps, int chunk, int prune,
-                      int coarsen, int lm, int shared, int dense_div, i32* lab) {
+                      int coarsen, int lm, int shared, int dense_div, double min_dq, i64* moves_out, i32* lab) {
     const int louv = algo == 0;
+    i64 all_moves = 0;
     i64* tot = (i64*)malloc(sizeof(i64) * (size_t)N);
     i32* csz = (i32*)malloc(sizeof(i32) * (size_t)N);
     i64* acc = (i64*)calloc((size_t)N, sizeof(i64));
@@ -1055,10 +1056,13 @@ static int tw_replica(int algo, i64 N, const i64* rowptr, const i32* col, const 
             prune_now = track_now;
             if (lm || moves * 4 < (unsigned long long)N) track_now = 1;
         }
-        if (louv) { if (moves == 0 || ((double)dq / 1099511627776.0) < 1e-7) active = 0; }
+        all_moves += (i64)moves;
+        /* min_dq: python-louvain's 1e-7; Leiden's level-0 move phase runs to exhaustion (0) */
+        if (louv) { if (moves == 0 || ((double)dq / 1099511627776.0) < min_dq) active = 0; }
         else if (unstable == 0) active = 0;
     }
     free(tot); free(csz); free(acc); free(seen); free(keys); free(dec); free(aff); free(mvf); free(lists); free(loff);
+    if (moves_out) *moves_out = all_moves;
     return sweep;
 }
 
@@ -1090,9 +1094,279 @@ void orc_engine_cd(int algo, i64 N, const i64* rowptr, const i32* col, const i32
 #pragma omp parallel for schedule(dynamic, 1)
     for (int r = 0; r < n_r; ++r) {
         int sw = tw_replica(algo, N, rowptr, col, cw, kdeg, M2, seed, (uint32_t)(rbase + r), (uint32_t)iteration,
-                            buckets, max_sweeps, chunk, prune, coarsen, lm, shared, dense_div, lab + (i64)r * N);
+                            buckets, max_sweeps, chunk, prune, coarsen, lm, shared, dense_div, 1e-7, NULL,
+                            lab + (i64)r * N);
         if (sweeps) sweeps[r] = sw;
     }
+    free(kdeg);
+}
+
+/* ==================================================================================
+ * CPU twin of the engine's multi-level Leiden (fastconsensus_amd/csrc/leiden.hip,
+ * multilevel(c, info = false, ...)), bit-exact target for its kernels.  One replica at a
+ * time, in the replica's LOCAL ids (the device's union id minus the replica's offset: every
+ * hash, tie break and id comparison of the device uses the local id).  Written from
+ * leiden.hip alone:
+ *   level 0 move phase  the Louvain engine twin (tw_replica, classic engine, per-replica
+ *                       orders) with the stop threshold at 0;
+ *   refine              one sweep of B buckets, bucket(x) = hash32(key ^ hash32(x)) % B with
+ *                       key = stream_key(seed, replica, iteration, level * 4096, 16 + 1); a
+ *                       vertex alone in its refined community joins the best refined community
+ *                       among its neighbours inside its move-phase community (lv_final); a
+ *                       bucket's decisions see the state the earlier buckets left, then apply;
+ *   aggregation         new ids = scan of the non-empty refined communities in id order; rows
+ *                       mapped through nid[R[.]], self loops dropped, weights summed; the new
+ *                       node starts in the smallest new id of its members' move-phase community;
+ *   explicit move       every vertex queued; sweeps of Bl buckets (key: level * 4096 + sweep + 1,
+ *                       salt 16 + 0) until one moves nothing; a mover requeues the neighbours
+ *                       whose community at the END of the bucket differs from its target;
+ *   final               lab[v] = P[memb[v]] at the level whose refinement merged nothing.
+ * Entry order inside a row never matters: sums commute and candidates are ranked by the total
+ * order (score, tie hash, id).
+ *
+ * trace (per replica, LT_TRACE int64): [0] levels; [1 + 8 * l + k] for level l < 64: k = 0
+ * vertices, 1 entries, 2 longest row, 3 move sweeps, 4 moves of the move phase, 5 moves of the
+ * refine sweep, 6 longest member-row sum of the aggregation that built the level; then, by
+ * row-length class (<= 64, 65..128, 129..512, 513..1024, 1025..2048, 2049..4096, longer),
+ * decisions [3 modes][7] at LT_DEC and applied moves [3][7] at LT_MOV (modes: 0 level-0 refine,
+ * 1 explicit refine, 2 explicit move), and the aggregated nodes by member-row sum [7] at LT_AGG.
+ * ================================================================================== */
+#define LT_LEVELS 64
+#define LT_NCLS 7
+#define LT_DEC (1 + 8 * LT_LEVELS)
+#define LT_MOV (LT_DEC + 3 * LT_NCLS)
+#define LT_AGG (LT_MOV + 3 * LT_NCLS)
+#define LT_TRACE (LT_AGG + LT_NCLS)
+int orc_leiden_trace_len(void) { return LT_TRACE; }
+#define LT_MOVE 0
+#define LT_REFINE 1
+typedef struct { i64 n, E; i64* rp; i32* col; i32* w; i64* kv; i64 maxdeg; } lt_graph;
+static inline int lt_class(i64 d) {
+    return d <= 64 ? 0 : d <= 128 ? 1 : d <= 512 ? 2 : d <= 1024 ? 3 : d <= 2048 ? 4 : d <= 4096 ? 5 : 6;
+}
+/* leiden.hip lv_better: larger score, then larger tie hash, then smaller id; c < 0 = none */
+static inline int lt_better(long long s1, uint32_t h1, i32 c1, long long s2, uint32_t h2, i32 c2) {
+    if (c1 < 0) return 0;
+    if (c2 < 0) return 1;
+    if (s1 != s2) return s1 > s2;
+    if (h1 != h2) return h1 > h2;
+    return c1 < c2;
+}
+static inline uint32_t lt_tie(uint32_t key, i64 x, i32 c) {
+    return tw_hash32(tw_hash32(key ^ 0x5bd1e995u ^ (uint32_t)x) ^ (uint32_t)c);
+}
+typedef struct { i64* acc; u8* seen; i32* keys; i32* mv; i32* mt; i32* bk; } lt_scratch;
+
+/* One sweep of B buckets in `mode` on level graph g.  lab: the labels the mode moves (P or R),
+ * tot: their totals.  Returns the applied moves. */
+static i64 lt_sweep(const lt_graph* g, i64 M2, int mode, uint32_t key, int B, i32* P, i32* R, i64* tot, i32* rsize,
+                    u8* act, lt_scratch* s, i64* dec_cls, i64* mov_cls) {
+    const i64 n = g->n;
+    i64 moves = 0;
+    for (i64 x = 0; x < n; ++x) s->bk[x] = (i32)(tw_hash32(key ^ tw_hash32((uint32_t)x)) % (uint32_t)B);
+    for (int b = 0; b < B; ++b) {
+        i64 nm = 0;
+        for (i64 x = 0; x < n; ++x) {
+            if (s->bk[x] != b) continue;
+            if (mode == LT_MOVE) {
+                if (!act[x]) continue;
+                act[x] = 0;                             /* popped from the queue */
+            } else if (rsize[R[x]] != 1) continue;      /* only nodes still alone in their refined community */
+            const i64 rb = g->rp[x], re = g->rp[x + 1];
+            dec_cls[lt_class(re - rb)]++;
+            const i32 own = mode == LT_REFINE ? R[x] : P[x], pc = P[x];
+            long long wown = 0;
+            i64 nk = 0;
+            for (i64 j = rb; j < re; ++j) {
+                const i32 y = g->col[j];
+                i32 c = P[y];
+                if (mode == LT_REFINE) c = c == pc ? R[y] : -1;
+                if (c < 0) continue;
+                const i32 w = g->w ? g->w[j] : 1;
+                if (c == own) { wown += w; continue; }
+                if (!s->seen[c]) { s->seen[c] = 1; s->acc[c] = 0; s->keys[nk++] = c; }   /* a weight may be 0 */
+                s->acc[c] += w;
+            }
+            const long long kvx = g->kv[x];
+            long long bs = 0; uint32_t bh = 0; i32 bc = -1;
+            for (i64 q = 0; q < nk; ++q) {
+                const i32 c = s->keys[q];
+                const long long sc = (long long)s->acc[c] * M2 - kvx * tot[c];
+                const uint32_t h = lt_tie(key, x, c);
+                if (lt_better(sc, h, c, bs, bh, bc)) { bs = sc; bh = h; bc = c; }
+                s->seen[c] = 0;
+            }
+            /* leiden.hip lv_final */
+            const long long stay = wown * M2 - kvx * (tot[own] - kvx);
+            i32 t = -1;
+            if (bc >= 0 && bs > stay) t = bc;
+            if (mode == LT_MOVE && stay < 0 && (t < 0 || bs < 0) && own != (i32)x && tot[x] == 0) t = (i32)x;
+            if (t >= 0) { s->mv[nm] = (i32)x; s->mt[nm] = t; ++nm; }
+        }
+        i32* lab = mode == LT_REFINE ? R : P;
+        for (i64 i = 0; i < nm; ++i) {
+            const i32 x = s->mv[i], t = s->mt[i], old = lab[x];
+            lab[x] = t;
+            tot[t] += g->kv[x];
+            tot[old] -= g->kv[x];
+            if (mode == LT_REFINE) { rsize[t]++; rsize[old]--; }
+            mov_cls[lt_class(g->rp[x + 1] - g->rp[x])]++;
+        }
+        /* queue flags from the bucket's final state: after every apply P[y] is y's target if it
+         * moved in this bucket and its (unchanged) community otherwise */
+        if (mode == LT_MOVE)
+            for (i64 i = 0; i < nm; ++i) {
+                const i32 x = s->mv[i], t = s->mt[i];
+                for (i64 j = g->rp[x]; j < g->rp[x + 1]; ++j)
+                    if (P[g->col[j]] != t) act[g->col[j]] = 1;
+            }
+        moves += nm;
+    }
+    return moves;
+}
+
+static void lt_replica(i64 N, const i64* rowptr, const i32* col, const i32* cw, const i64* kdeg, i64 M2, u64 seed,
+                       uint32_t rg, uint32_t iter, int buckets, int level_buckets, int max_sweeps, int chunk,
+                       int prune, int coarsen, int lm, i32* lab, i64* tr) {
+    memset(tr, 0, sizeof(i64) * LT_TRACE);
+    const int B = buckets > 0 ? buckets : 32;                                /* refine sweeps */
+    const int Bl = (buckets == 0 && level_buckets > 0) ? level_buckets : B;   /* explicit move sweeps */
+    i64 mv0 = 0;
+    const int sw0 = tw_replica(0, N, rowptr, col, cw, kdeg, M2, seed, rg, iter, buckets > 0 ? buckets : 16, max_sweeps,
+                               chunk, prune, coarsen, lm, 0, 0, 0.0, &mv0, lab);
+    lt_graph g;
+    g.n = N; g.E = rowptr[N]; g.rp = (i64*)rowptr; g.col = (i32*)col; g.w = (i32*)cw; g.kv = (i64*)kdeg; g.maxdeg = 0;
+    for (i64 v = 0; v < N; ++v) if (rowptr[v + 1] - rowptr[v] > g.maxdeg) g.maxdeg = rowptr[v + 1] - rowptr[v];
+    int owned = 0;   /* g's arrays are this function's (levels >= 1) */
+    i32* P = (i32*)malloc(sizeof(i32) * (size_t)N);
+    i32* R = (i32*)malloc(sizeof(i32) * (size_t)N);
+    i64* rtot = (i64*)malloc(sizeof(i64) * (size_t)N);
+    i64* ptot = (i64*)malloc(sizeof(i64) * (size_t)N);
+    i32* rsize = (i32*)malloc(sizeof(i32) * (size_t)N);
+    i32* memb = (i32*)malloc(sizeof(i32) * (size_t)N);
+    i32* nid = (i32*)malloc(sizeof(i32) * (size_t)(N + 1));
+    i32* prep = (i32*)malloc(sizeof(i32) * (size_t)N);
+    i32* pofR = (i32*)malloc(sizeof(i32) * (size_t)N);
+    i32* moff = (i32*)malloc(sizeof(i32) * (size_t)(N + 2));
+    i32* mlist = (i32*)malloc(sizeof(i32) * (size_t)N);
+    u8* act = (u8*)malloc((size_t)N);
+    lt_scratch s;
+    s.acc = (i64*)calloc((size_t)N, sizeof(i64));
+    s.seen = (u8*)calloc((size_t)N, 1);
+    s.keys = (i32*)malloc(sizeof(i32) * (size_t)N);
+    s.mv = (i32*)malloc(sizeof(i32) * (size_t)N);
+    s.mt = (i32*)malloc(sizeof(i32) * (size_t)N);
+    s.bk = (i32*)malloc(sizeof(i32) * (size_t)N);
+    for (i64 v = 0; v < N; ++v) { P[v] = lab[v]; memb[v] = (i32)v; }
+    tr[1 + 3] = sw0; tr[1 + 4] = mv0;
+    int level = 0;
+    for (;; ++level) {
+        const i64 n = g.n;
+        if (level < LT_LEVELS) { i64* t = tr + 1 + 8 * level; t[0] = n; t[1] = g.E; t[2] = g.maxdeg; }
+        /* ---- refine: singletons inside the move-phase communities, one sweep */
+        for (i64 x = 0; x < n; ++x) { R[x] = (i32)x; rtot[x] = g.kv[x]; rsize[x] = 1; }
+        const int rm = level == 0 ? 0 : 1;
+        const i64 rmv = lt_sweep(&g, M2, LT_REFINE, tw_stream_key(seed, rg, iter, (uint32_t)(level * 4096), 16 + LT_REFINE),
+                                 B, P, R, rtot, rsize, NULL, &s, tr + LT_DEC + rm * LT_NCLS, tr + LT_MOV + rm * LT_NCLS);
+        if (level < LT_LEVELS) tr[1 + 8 * level + 5] = rmv;
+        /* ---- refined communities < level nodes: aggregate; else this level's P is final */
+        i32 nn = 0;
+        for (i64 c = 0; c < n; ++c) { nid[c] = nn; nn += rsize[c] > 0; }
+        nid[n] = nn;
+        if (nn == n || level + 1 >= LT_LEVELS) break;
+        lt_graph nx;
+        nx.n = nn;
+        nx.rp = (i64*)malloc(sizeof(i64) * (size_t)(nn + 1));
+        nx.kv = (i64*)malloc(sizeof(i64) * (size_t)nn);
+        for (i64 c = 0; c < n; ++c) if (rsize[c] > 0) nx.kv[nid[c]] = rtot[c];
+        /* members of every new node (counting sort by new id) */
+        for (i32 k = 0; k <= nn + 1; ++k) moff[k] = 0;
+        for (i64 x = 0; x < n; ++x) moff[nid[R[x]] + 2]++;
+        for (i32 k = 0; k < nn; ++k) moff[k + 2] += moff[k + 1];
+        for (i64 x = 0; x < n; ++x) mlist[moff[nid[R[x]] + 1]++] = (i32)x;
+        /* pofR[R[x]] = P[x]; prep[P] = smallest new id among the community's members */
+        for (i64 c = 0; c < n; ++c) prep[c] = 0x7fffffff;
+        for (i64 x = 0; x < n; ++x) {
+            pofR[R[x]] = P[x];
+            if (nid[R[x]] < prep[P[x]]) prep[P[x]] = nid[R[x]];
+        }
+        /* rows: the members' rows through nid[R[.]], self loops dropped, weights summed */
+        i64 cap = g.E > 0 ? g.E : 1, E = 0, ubmax = 0;
+        nx.col = (i32*)malloc(sizeof(i32) * (size_t)cap);
+        nx.w = (i32*)malloc(sizeof(i32) * (size_t)cap);
+        nx.maxdeg = 0;
+        for (i32 xn = 0; xn < nn; ++xn) {
+            nx.rp[xn] = E;
+            i64 nk = 0, ub = 0;
+            for (i32 q = moff[xn]; q < moff[xn + 1]; ++q) {
+                const i32 x = mlist[q];
+                ub += g.rp[x + 1] - g.rp[x];
+                for (i64 j = g.rp[x]; j < g.rp[x + 1]; ++j) {
+                    const i32 yn = nid[R[g.col[j]]];
+                    if (yn == xn) continue;
+                    if (!s.seen[yn]) { s.seen[yn] = 1; s.acc[yn] = 0; s.keys[nk++] = yn; }
+                    s.acc[yn] += g.w ? g.w[j] : 1;
+                }
+            }
+            for (i64 q = 0; q < nk; ++q) {
+                nx.col[E] = s.keys[q]; nx.w[E] = (i32)s.acc[s.keys[q]]; s.seen[s.keys[q]] = 0; ++E;
+            }
+            tr[LT_AGG + lt_class(ub)]++;
+            if (ub > ubmax) ubmax = ub;
+            if (nk > nx.maxdeg) nx.maxdeg = nk;
+        }
+        nx.rp[nn] = E;
+        nx.E = E;
+        /* the new level's P, the input vertices' members */
+        for (i64 c = 0; c < n; ++c) if (rsize[c] > 0) s.mt[nid[c]] = prep[pofR[c]];
+        for (i64 v = 0; v < N; ++v) memb[v] = nid[R[memb[v]]];
+        for (i32 k = 0; k < nn; ++k) P[k] = s.mt[k];
+        if (owned) { free(g.rp); free(g.col); free(g.w); free(g.kv); }
+        g = nx;
+        owned = 1;
+        if (level + 1 < LT_LEVELS) tr[1 + 8 * (level + 1) + 6] = ubmax;
+        /* ---- move phase on the new level, from the inherited partition, until no move */
+        for (i32 k = 0; k < nn; ++k) { ptot[k] = 0; act[k] = 1; }
+        for (i32 k = 0; k < nn; ++k) ptot[P[k]] += g.kv[k];
+        int sw = 0;
+        i64 lmoves = 0;
+        for (; sw < max_sweeps; ++sw) {
+            const i64 mvs = lt_sweep(&g, M2, LT_MOVE,
+                                     tw_stream_key(seed, rg, iter, (uint32_t)((level + 1) * 4096 + sw + 1), 16 + LT_MOVE),
+                                     Bl, P, R, ptot, rsize, act, &s, tr + LT_DEC + 2 * LT_NCLS, tr + LT_MOV + 2 * LT_NCLS);
+            lmoves += mvs;
+            if (mvs == 0) { ++sw; break; }
+        }
+        if (level + 1 < LT_LEVELS) { tr[1 + 8 * (level + 1) + 3] = sw; tr[1 + 8 * (level + 1) + 4] = lmoves; }
+    }
+    tr[0] = level + 1;
+    for (i64 v = 0; v < N; ++v) lab[v] = P[memb[v]];
+    if (owned) { free(g.rp); free(g.col); free(g.w); free(g.kv); }
+    free(P); free(R); free(rtot); free(ptot); free(rsize); free(memb); free(nid); free(prep); free(pofR); free(moff);
+    free(mlist); free(act); free(s.acc); free(s.seen); free(s.keys); free(s.mv); free(s.mt); free(s.bk);
+}
+
+/* Replicas [rbase, rbase+n_r) of the engine's Leiden on a symmetric CSR with weights cw.
+ * buckets: FC_OPT_BUCKETS (0: the defaults -- 16 for the level-0 move phase, 32 for refine,
+ * level_buckets for the explicit move sweeps); the level-0 engine arguments are engine_cd's.
+ * lab: [n_r][N] community ids (local ids of the final level), trace: [n_r][LT_TRACE]. */
+void orc_engine_leiden(i64 N, const i64* rowptr, const i32* col, const i32* cw, int n_r, int rbase, int iteration,
+                       u64 seed, int buckets, int level_buckets, int max_sweeps, int chunk, int prune, int coarsen,
+                       int prune_mark, i32* lab, i64* trace) {
+    i64* kdeg = (i64*)malloc(sizeof(i64) * (size_t)(N ? N : 1));
+    i64 M2 = 0;
+    i32 max_w = 0;
+    for (i64 v = 0; v < N; ++v) {
+        i64 sum = 0;
+        for (i64 j = rowptr[v]; j < rowptr[v + 1]; ++j) { sum += cw[j]; if (cw[j] > max_w) max_w = cw[j]; }
+        kdeg[v] = sum;
+        M2 += sum;
+    }
+    const int lm = (max_w > 1 || prune_mark == 2) && prune && prune_mark >= 1;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int r = 0; r < n_r; ++r)
+        lt_replica(N, rowptr, col, cw, kdeg, M2, seed, (uint32_t)(rbase + r), (uint32_t)iteration, buckets,
+                   level_buckets, max_sweeps, chunk, prune, coarsen, lm, lab + (i64)r * N, trace + (i64)r * LT_TRACE);
     free(kdeg);
 }
 

@@ -76,6 +76,10 @@ def lib():
         L.orc_engine_cd.argtypes = [ctypes.c_int, i64, _i64p, _i32p, _i32p, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_int, u64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _i32p]
+        L.orc_engine_leiden.argtypes = [i64, _i64p, _i32p, _i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, u64,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, _i32p, _i64p]
+        L.orc_leiden_trace_len.restype = ctypes.c_int
         L.orc_device_sigma.argtypes = [i64, u64, _i32p]
         L.orc_set_lpa_ties.argtypes = [ctypes.c_int]
         L.orc_set_lpa_coarsen.argtypes = [ctypes.c_int]
@@ -322,6 +326,57 @@ def engine_cd(algo, g, n_r, rbase, iteration, seed, buckets=None, max_sweeps=200
     lib().orc_engine_cd(_cd_algo(algo), g.N, rowptr, col, cw, n_r, rbase, iteration, int(seed) & (2**64 - 1), buckets,
                         max_sweeps, chunk, prune, coarsen, prune_mark, shared, dense_div, lab, sw)
     return lab, sw
+
+
+# row-length classes of the Leiden kernels (leiden.hip): k_lv_decide<512, 4>, <512, 2>, <LWS, 1>, the
+# three LDS tiers of k_lv_heavy / k_ag_rows_heavy and their global-table tier
+LEIDEN_CLASSES = ("<=64", "65..128", "129..512", "513..1024", "1025..2048", "2049..4096", ">4096")
+LEIDEN_MODES = ("refine0", "refine", "move")   # level-0 refine, explicit refine, explicit move
+LEVEL_BUCKETS = 4   # the engine's default buckets per explicit move sweep (fc_ctx.h lv_level_b)
+
+
+def leiden_class(d):
+    """Row-length class (index into LEIDEN_CLASSES) of a row / member-row sum of d entries."""
+    return int(np.searchsorted([64, 128, 512, 1024, 2048, 4096], d))
+
+
+class LeidenTrace:
+    """One replica's trace of engine_leiden: `levels`, per level `vertices`, `entries`,
+    `longest_row`, `move_sweeps`, `moves` (move phase), `refine_moves`, `member_sum` (the longest
+    member-row sum of the aggregation that built the level); `decisions[mode][class]` and
+    `moved[mode][class]` (modes LEIDEN_MODES, classes LEIDEN_CLASSES); `agg[class]`: aggregated
+    nodes by member-row sum."""
+
+    def __init__(self, t):
+        self.levels = int(t[0])
+        lv = t[1:1 + 8 * 64].reshape(64, 8)[:self.levels]
+        (self.vertices, self.entries, self.longest_row, self.move_sweeps, self.moves, self.refine_moves,
+         self.member_sum) = (lv[:, k].copy() for k in range(7))
+        o = 1 + 8 * 64
+        self.decisions = t[o:o + 21].reshape(3, 7).copy()
+        self.moved = t[o + 21:o + 42].reshape(3, 7).copy()
+        self.agg = t[o + 42:o + 49].copy()
+
+    def summary(self):
+        cls = lambda a: "+".join(LEIDEN_CLASSES[k] for k in range(7) if a[k]) or "-"
+        return "%d levels, longest rows %s, decided %s, moved %s, member sums %s" % (
+            self.levels, list(map(int, self.longest_row)),
+            " ".join("%s:%s" % (m, cls(self.decisions[i])) for i, m in enumerate(LEIDEN_MODES)),
+            " ".join("%s:%s" % (m, cls(self.moved[i])) for i, m in enumerate(LEIDEN_MODES)), cls(self.agg))
+
+
+def engine_leiden(g, n_r, rbase, iteration, seed, buckets=0, level_buckets=LEVEL_BUCKETS, max_sweeps=200, chunk=16,
+                  prune=1, coarsen=8, prune_mark=1):
+    """CPU twin of the engine's multi-level Leiden (leiden.hip; bit-exact target): replicas
+    [rbase, rbase + n_r) on g (its weights).  buckets = FC_OPT_BUCKETS (0: the engine's defaults);
+    the level-0 arguments are engine_cd's.  Returns (labels [n_r][N], [LeidenTrace] * n_r)."""
+    rowptr, col, cw = g.csr()
+    lab = np.empty((n_r, g.N), np.int32)
+    tl = lib().orc_leiden_trace_len()
+    tr = np.zeros((n_r, tl), np.int64)
+    lib().orc_engine_leiden(g.N, rowptr, col, cw, n_r, rbase, iteration, int(seed) & (2**64 - 1), int(buckets or 0),
+                            level_buckets, max_sweeps, chunk, prune, coarsen, prune_mark, lab, tr)
+    return lab, [LeidenTrace(t) for t in tr]
 
 
 def renumber(labels):

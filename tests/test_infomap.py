@@ -20,28 +20,9 @@ import pytest
 
 from oracle import oracle as orc
 from tests import golden_io
+from tests.leiden_graphs import codelength   # the two-level map equation, float64
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def plogp(p):
-    p = np.asarray(p, np.float64)
-    out = np.zeros_like(p)
-    nz = p > 0
-    out[nz] = p[nz] * np.log2(p[nz])
-    return out
-
-
-def codelength(N, e, lab):
-    """Two-level map equation (bits) of a partition of an unweighted undirected graph."""
-    deg = np.bincount(e.ravel(), minlength=N).astype(np.float64)
-    W = deg.sum()
-    k = int(lab.max()) + 1
-    tot = np.bincount(lab, weights=deg, minlength=k)
-    cut = lab[e[:, 0]] != lab[e[:, 1]]
-    out = np.bincount(lab[e[cut, 0]], minlength=k) + np.bincount(lab[e[cut, 1]], minlength=k)
-    q, p = out / W, tot / W
-    return float(plogp(q.sum()) - 2 * plogp(q).sum() - plogp(deg / W).sum() + plogp(q + p).sum())
 
 
 def nmi(a, b):

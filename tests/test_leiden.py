@@ -122,6 +122,117 @@ def test_reference_leiden_branch_exit(name):
         assert len(np.unique(np.stack([a, b], 1), axis=0)) == len(np.unique(a)) == len(np.unique(b))
 
 
+# ------------------------------------------------------------------------------ CPU: the twin
+# orc.engine_leiden restates leiden.hip sequentially (oracle/fc_oracle.c orc_engine_leiden); the
+# device is compared with it label for label in tests/test_gpu_leiden_twin.py.  Here: the twin
+# itself is a sound Leiden, does not depend on what the device's hash tables may reorder, and the
+# graphs of the GPU comparison reach the kernel paths they are meant to reach.
+def _lfr1k():
+    case = golden_io.load("lfr1k_louvain_np20")
+    return case.N, case.edges_file
+
+
+def test_twin_lfr1k_vs_restatement():
+    """Tolerances of test_leiden_lfr1k_vs_restatement (the device's): mean modularity within 0.01
+    of the sequential restatement, community count within 25 %; every community connected,
+    labels contiguous after renumbering and within [0, n) before."""
+    n, e = _lfr1k()
+    g = orc.EdgeGraph.from_lines(n, e)
+    tw, tr = orc.engine_leiden(g, 16, 0, 0, 11)
+    ref, _ = orc.cd_batch(orc.LEIDEN, 16, g, seed=5)
+    qt, qr = (np.mean([orc.modularity(g, x) for x in L]) for L in (tw, ref))
+    kt, kr = (np.mean([len(np.unique(x)) for x in L]) for L in (tw, ref))
+    print("twin LFR-1k Q %.4f k %.1f | restatement Q %.4f k %.1f" % (qt, kt, qr, kr))
+    assert abs(qt - qr) <= 0.01
+    assert abs(kt - kr) <= 0.25 * kr
+    assert all(t.levels >= 2 for t in tr)
+    for x, y in zip(tw, orc.renumber(tw)):
+        assert x.min() >= 0 and x.max() < n
+        assert connected_communities(n, e, x)
+        assert y.min() == 0 and y.max() + 1 == len(np.unique(x))
+
+
+@pytest.mark.parametrize("graph", ["lfr1k", 700])
+def test_twin_independent_of_row_entry_order(graph):
+    """Permuting the entries inside every CSR row leaves every label unchanged: sums commute and
+    candidates are ranked by a total order, the stated reason why the device's hash-table order
+    (aggregated rows) cannot matter."""
+    from tests.leiden_graphs import hub_cliques
+    n, e = _lfr1k() if graph == "lfr1k" else hub_cliques(graph, seed=3)
+    g = orc.EdgeGraph.from_lines(n, e)
+    rng = np.random.default_rng(5)
+    if graph == "lfr1k":                                        # the weighted path too
+        g = orc.EdgeGraph(n, g.u, g.v, rng.integers(1, 4, g.m), g.age)
+    rowptr, col, cw = g.csr()
+    col2, cw2 = col.copy(), cw.copy()
+    for v in range(n):
+        p = rng.permutation(int(rowptr[v + 1] - rowptr[v])) + rowptr[v]
+        col2[rowptr[v]:rowptr[v + 1]], cw2[rowptr[v]:rowptr[v + 1]] = col[p], cw[p]
+    assert not np.array_equal(col, col2)
+
+    class Shuffled:
+        N = n
+
+        def __init__(self, c, w):
+            self.c, self.w = c, w
+
+        def csr(self):
+            return rowptr, self.c, self.w
+    a, _ = orc.engine_leiden(Shuffled(col, cw), 4, 0, 2, 23)
+    b, _ = orc.engine_leiden(Shuffled(col2, cw2), 4, 0, 2, 23)
+    assert np.array_equal(a, b)
+
+
+def test_twin_independent_of_sharding():
+    """Replicas 2..4 of a 6-replica batch equal the same replicas computed alone."""
+    n, e = _lfr1k()
+    g = orc.EdgeGraph.from_lines(n, e)
+    full, _ = orc.engine_leiden(g, 6, 0, 1, 99)
+    part, _ = orc.engine_leiden(g, 3, 2, 1, 99)
+    assert np.array_equal(full[2:5], part)
+    assert len({x.tobytes() for x in full}) > 1                 # the replicas differ
+
+
+def test_twin_louvain_threshold_parameter():
+    """tw_replica's stop threshold is a parameter now: engine_cd keeps python-louvain's 1e-7, so
+    its labels are what they were (golden: the twin's own earlier output is the device's, checked
+    bit for bit by the GPU parity tests); Leiden's level 0 runs on past it."""
+    n, e = _lfr1k()
+    g = orc.EdgeGraph.from_lines(n, e)
+    _, sw = orc.engine_cd(0, g, 4, 0, 0, 7, shared=0)
+    _, tr = orc.engine_leiden(g, 4, 0, 0, 7)
+    assert all(int(t.move_sweeps[0]) >= int(s) for t, s in zip(tr, sw))
+
+
+def test_gpu_twin_cases_reach_their_paths():
+    """The preconditions of tests/test_gpu_leiden_twin.py, from the twin's trace (no GPU): a graph
+    that stops reaching the kernel path it is there for fails here, on any machine."""
+    from tests.leiden_graphs import LEIDEN_CASES, G2_OFF_CASE, leiden_twin, weighted_graph_cpu
+    heavy_move = heavy_refine = levels_differ = False
+    for case in LEIDEN_CASES + [G2_OFF_CASE]:
+        lab, tr = leiden_twin(case)
+        dec = sum(t.decisions for t in tr)
+        mov = sum(t.moved for t in tr)
+        agg = sum(t.agg for t in tr)
+        print(case.id, "|", " || ".join(t.summary() for t in tr))
+        assert all(t.levels >= 2 for t in tr), case.id                        # at least two levels everywhere
+        levels_differ |= len({t.levels for t in tr}) > 1
+        if case.graph == "lfr1k_weighted":
+            assert weighted_graph_cpu(case)[3].max() > 1, "no weight past 1: not the weighted path"
+        if case.d > 64:
+            k = orc.leiden_class(case.d)
+            assert (dec[:, k] > 0).all(), (case.id, dec.tolist())              # its class, in all three modes
+        if case.d > 512:
+            k = orc.leiden_class(case.d)
+            assert agg[k] > 0, (case.id, agg.tolist())                         # a member-row sum in its tier
+            heavy_move |= bool(mov[2, 3:].any())
+            heavy_refine |= bool(mov[:2, 3:].any())
+    # a heavy kernel that always answers "stay" would be caught: heavy rows do move, in both modes
+    assert heavy_move and heavy_refine
+    # the path that drops finished replicas and rescans: a batch whose replicas finish at different levels
+    assert levels_differ
+
+
 # ------------------------------------------------------------------------------ device
 torch = pytest.importorskip("torch")
 
