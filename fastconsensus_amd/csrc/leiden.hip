@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <chrono>
 #include <climits>
+#include <type_traits>
 #include <vector>
 
 #include "fc_ctx.h"
@@ -53,6 +54,16 @@ constexpr int HLIGHT = HLS / 2;   // longer rows use a global table
 // blocks per CU.
 constexpr int NTIER = 4;
 __host__ __device__ constexpr int heavy_tier(int64_t d) { return d <= 1024 ? 0 : d <= 2048 ? 1 : d <= 4096 ? 2 : 3; }
+// The launches of a level whose longest row has `longest` (> LIGHT) entries: f(slots, grid, tier)
+// for every tier up to that row's, slots as a compile-time constant.  Tier 3 runs on `hg` blocks
+// (LvRun::heavy_grid) with one global table each, so it takes the smallest LDS table.
+template <class F> void for_heavy_tiers(int64_t longest, int hg, F&& f) {
+    const int top = heavy_tier(longest);
+    f(std::integral_constant<int, 2048>{}, 2048, 0);
+    if (top >= 1) f(std::integral_constant<int, 4096>{}, 1280, 1);
+    if (top >= 2) f(std::integral_constant<int, HLS>{}, 512, 2);
+    if (top >= 3) f(std::integral_constant<int, 2048>{}, hg, 3);
+}
 constexpr int MODE_MOVE = 0, MODE_REFINE = 1, MODE_INFO = 2;   // Leiden move / refine; Infomap move
 constexpr int MSH = 256;          // move-counter shards
 constexpr int MAX_LEVELS = 64;
@@ -1220,118 +1231,129 @@ struct LvGraph {
     int32_t max_deg = 0;
 };
 
-}  // namespace
+// This file's read-back slots in the pinned scratch Ctx::hpin (int64 units).
+constexpr int HP_AG = 40;     // aggregation: [0] member-row sum total, later the new level's entries, [1] the longest
+                              // member-row sum (bounds the heavy tables), [2] longest new row, [3] rows listed as heavy
+constexpr int HP_LONG = 48;   // bind_level: the level's rows past 64 entries
+// B_MISC (int32 units): [n_r] refined-community counts | [n_r] finalize flags (u8 view) | 2 u64 maxima
+constexpr int64_t misc_fin(int n_r) { return n_r; }
+constexpr int64_t misc_max(int n_r) { return 2 * (int64_t)n_r + 2 + ((2 * n_r) & 1); }   // 8-byte aligned
+constexpr int64_t misc_len(int n_r) { return 2 * (int64_t)n_r + 16; }
 
-// One multi-level run per local replica on the working graph c.g; labels -> lab_out (slot
-// order, values in [0, N) per replica), exactly like cd_run leaves c.lab.
-//   info = false: Leiden (level-0 move on the Louvain engine, refine, aggregate by R);
-//   info = true:  `tu` Infomap trials per replica side by side in the union (union replica
-//                 u = r*tu + j runs trial trial0 + j of replica r: the same random streams as
-//                 running the trials one after the other); map-equation passes at every
-//                 level, aggregation by the modules; cl_out[u] = its codelength (without the
-//                 constant node-entropy term) for the best-of-trials choice.
-static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total, int iteration, int tu, int trial0,
-                       int32_t* lab_out, double* cl_out) {
-    FC_REQUIRE(rcount >= 1 && rbegin >= 0 && rbegin + rcount <= n_p_total, FC_EINVAL, "bad replica range");
-    FC_REQUIRE(c.N > 0 && c.g.rowptr.p, FC_ESTATE, "no graph loaded");
-    const int64_t N = c.N;
-    Graph& g = c.g;
-    // Infomap runs on the topology (community_infomap() without weights, :268 / :390)
-    const int64_t M2 = info ? 2 * g.m : g.M2;
-    FC_REQUIRE(M2 < 0x7fffffffll, FC_ELIMIT, "leiden/infomap: total edge weight must stay below 2^30");
-    FC_REQUIRE(tu >= 1 && (info || tu == 1), FC_EINVAL, "trials side by side are for Infomap");
-    FC_REQUIRE((int64_t)rcount * tu * N < 0x7fffffffll, FC_ELIMIT,
-               "leiden/infomap: replicas x trials x nodes must stay below 2^31");
+// f(IMPL) / f(IMPL, MODE) with the run-time values as compile-time constants, for the kernels'
+// template arguments.  The input-graph level has no Leiden move sweep (cd_run is its move phase).
+template <class F> void dispatch(bool impl, F&& f) {
+    if (impl) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F> void dispatch(bool impl, int mode, F&& f) {
+    FC_REQUIRE(!(impl && mode == MODE_MOVE), FC_ESTATE, "leiden: no move sweep on the input-graph level");
+    if (mode == MODE_MOVE) f(std::false_type{}, std::integral_constant<int, MODE_MOVE>{});
+    else if (mode == MODE_REFINE) dispatch(impl, [&](auto im) { f(im, std::integral_constant<int, MODE_REFINE>{}); });
+    else dispatch(impl, [&](auto im) { f(im, std::integral_constant<int, MODE_INFO>{}); });
+}
 
-    if (!info) {
-        // ---- level 0, move phase: the replica-batched local-moving engine run to exhaustion
-        const double mdq = c.cd_min_dq;
-        c.cd_min_dq = 0.0;
-        try {
-            cd_run(c, FC_ALGO_LOUVAIN, rbegin, rcount, n_p_total, iteration);
-        } catch (...) {
-            c.cd_min_dq = mdq;
-            throw;
-        }
-        c.cd_min_dq = mdq;
-    }
-    // lab_out == nullptr: c.lab, read only now (cd_run above may have (re)allocated it)
-    if (!lab_out) lab_out = ensure<int32_t>(c.lab, (size_t)rcount * (size_t)N);
-    const int sl0 = timer_begin(c);   // (cd_run timed itself) refinement, Infomap passes and the levels
-    const char* name = info ? "infomap" : "leiden";
+struct RestoreMinDq {   // cd_min_dq back to the caller's value, also when cd_run throws
+    Ctx& c;
+    const double v;
+    ~RestoreMinDq() { c.cd_min_dq = v; }
+};
 
-    const int n_r = rcount * tu;   // union replicas
-    const int64_t nU0 = (int64_t)n_r * N;
-    const int B = std::max(1, c.buckets > 0 ? c.buckets : CD_BUCKETS_LPA);   // refine / Infomap sweeps (level 0 Louvain: cd_buckets)
-    auto I32 = [&](int k, int64_t n) { return ensure<int32_t>(c.lv[k], (size_t)std::max<int64_t>(n, 1)); };
-    auto I64 = [&](int k, int64_t n) { return ensure<int64_t>(c.lv[k], (size_t)std::max<int64_t>(n, 1)); };
-    auto U8 = [&](int k, int64_t n) { return ensure<uint8_t>(c.lv[k], (size_t)std::max<int64_t>(n, 1)); };
-
-    int32_t* P = I32(B_P, nU0);
-    int32_t* R = I32(B_R, nU0);
-    int64_t* rtot = I64(B_RTOT, nU0);
-    int32_t* rsize = I32(B_RSIZE, nU0);
-    int32_t* memb = I32(B_MEMB, nU0);
-    uint8_t* done = U8(B_DONE, n_r);
-    int32_t* roff = I32(B_ROFF, n_r);
-    int32_t* rend = I32(B_REND, n_r);
-    uint32_t* rkey = (uint32_t*)I32(B_RKEY, n_r);
-    unsigned long long* moves = (unsigned long long*)I64(B_MOVES, MSH);
-    int32_t* hcnt = I32(B_HCNT, 4);
-    // [n_r] refined-community counts | [n_r] finalize flags (u8 view) | 2 u64 maxima
-    int32_t* misc = I32(B_MISC, 2 * (int64_t)n_r + 16);
-    FC_HIP(hipMemsetAsync(done, 0, n_r, c.stream));
-    int64_t* deg = nullptr;
+// The state of one multilevel() run; its methods are the phases, in the order multilevel() calls
+// them.  ensure() may reallocate, so a device pointer kept here is re-read after every ensure()
+// on its slot (bind_level, aggregate and move_phase do so for the slots they reuse).
+struct LvRun {
+    Ctx& c;
+    Graph& g;
+    const bool info;
+    const int rbegin, tu, trial0, iteration, n_r;
+    const int64_t N, nU0;
+    const int B;              // buckets of the refine / Infomap sweeps (level 0 Louvain: cd_buckets)
+    int32_t* const lab_out;
+    LvArgs a{};
+    LvGraph cur;              // explicit level (level >= 1)
+    int pp = 0;               // ping-pong slot of the next explicit level
+    bool impl = true;
+    int64_t nU;
+    int32_t max_deg;
+    std::vector<int32_t> h_roff, h_rend, h_icnt;
+    std::vector<uint8_t> h_done;
+    std::vector<uint32_t> h_rkey;
+    uint32_t stamp_ctr = 0;
+    int64_t lv_sweeps = 0;
+    unsigned long long pd = 0, ph = 0;   // trace: decide / heavy bytes up to the previous move sweep
+    int32_t *P, *R, *rsize, *memb, *roff, *rend, *hcnt, *misc, *nid = nullptr, *fl = nullptr;
+    int64_t *rtot, *deg = nullptr, *qrep = nullptr;
     int64_t* ptot = nullptr;   // Leiden: move-phase community totals
     int64_t* mod = nullptr;    // Infomap: {flow, exit weight} per module
-    int64_t* qrep = nullptr;
     double* dcl = nullptr;
-    if (info) {
-        deg = I64(B_DEG, N);
-        mod = I64(B_POUT, 2 * nU0);
-        qrep = I64(B_QREP, n_r);
-        dcl = (double*)I64(B_CL, n_r);
-        k_degree<<<nb(N), LTB, 0, c.stream>>>(N, g.rowptr.as<int64_t>(), deg);
-        k_info_init0<<<nb(nU0), LTB, 0, c.stream>>>(N, n_r, deg, P, mod, memb);
-        std::vector<int64_t> q0(n_r, M2);   // singletons: total exit weight = every edge end
-        FC_HIP(hipMemcpyAsync(qrep, q0.data(), 8 * (size_t)n_r, hipMemcpyHostToDevice, c.stream));
-        sync(c);
-    } else {
-        k_lv_init0<<<nb(nU0), LTB, 0, c.stream>>>(N, n_r, c.lab.as<int32_t>(), c.spos.as<int32_t>(), P, R, rtot,
-                                                   rsize, g.kdeg.as<int64_t>(), memb);
+    uint8_t* done;
+    uint32_t* rkey;
+    unsigned long long* moves;
+
+    int32_t* I32(int k, int64_t n) { return ensure<int32_t>(c.lv[k], (size_t)std::max<int64_t>(n, 1)); }
+    int64_t* I64(int k, int64_t n) { return ensure<int64_t>(c.lv[k], (size_t)std::max<int64_t>(n, 1)); }
+    uint8_t* U8(int k, int64_t n) { return ensure<uint8_t>(c.lv[k], (size_t)std::max<int64_t>(n, 1)); }
+
+    // set-up: the run's buffers, the level-0 partition (Infomap: singletons; Leiden: cd_run's labels)
+    // and the launch arguments that hold for every level
+    LvRun(Ctx& c_, bool info_, int rbegin_, int rcount, int iteration_, int tu_, int trial0_, int64_t M2,
+          int32_t* lab_out_)
+        : c(c_), g(c_.g), info(info_), rbegin(rbegin_), tu(tu_), trial0(trial0_), iteration(iteration_),
+          n_r(rcount * tu_), N(c_.N), nU0((int64_t)n_r * N),
+          B(std::max(1, c_.buckets > 0 ? c_.buckets : CD_BUCKETS_LPA)), lab_out(lab_out_), nU(nU0),
+          max_deg(c_.g.max_deg), h_roff(n_r), h_rend(n_r), h_done(n_r, 0), h_rkey(n_r) {
+        P = I32(B_P, nU0);
+        R = I32(B_R, nU0);
+        rtot = I64(B_RTOT, nU0);
+        rsize = I32(B_RSIZE, nU0);
+        memb = I32(B_MEMB, nU0);
+        done = U8(B_DONE, n_r);
+        roff = I32(B_ROFF, n_r);
+        rend = I32(B_REND, n_r);
+        rkey = (uint32_t*)I32(B_RKEY, n_r);
+        moves = (unsigned long long*)I64(B_MOVES, MSH);
+        hcnt = I32(B_HCNT, 4);
+        misc = I32(B_MISC, misc_len(n_r));
+        FC_HIP(hipMemsetAsync(done, 0, n_r, c.stream));
+        if (info) {
+            deg = I64(B_DEG, N);
+            mod = I64(B_POUT, 2 * nU0);
+            qrep = I64(B_QREP, n_r);
+            dcl = (double*)I64(B_CL, n_r);
+            k_degree<<<nb(N), LTB, 0, c.stream>>>(N, g.rowptr.as<int64_t>(), deg);
+            k_info_init0<<<nb(nU0), LTB, 0, c.stream>>>(N, n_r, deg, P, mod, memb);
+            std::vector<int64_t> q0(n_r, M2);   // singletons: total exit weight = every edge end
+            FC_HIP(hipMemcpyAsync(qrep, q0.data(), 8 * (size_t)n_r, hipMemcpyHostToDevice, c.stream));
+            sync(c);
+        } else {
+            k_lv_init0<<<nb(nU0), LTB, 0, c.stream>>>(N, n_r, c.lab.as<int32_t>(), c.spos.as<int32_t>(), P, R, rtot,
+                                                       rsize, g.kdeg.as<int64_t>(), memb);
+        }
+        for (int r = 0; r < n_r; ++r) { h_roff[r] = (int32_t)(r * N); h_rend[r] = (int32_t)((r + 1) * N); }
+        FC_HIP(hipMemcpyAsync(roff, h_roff.data(), 4 * (size_t)n_r, hipMemcpyHostToDevice, c.stream));
+        FC_HIP(hipMemcpyAsync(rend, h_rend.data(), 4 * (size_t)n_r, hipMemcpyHostToDevice, c.stream));
+
+        a.N0 = N; a.M2 = M2; a.B = B;
+        a.inv = M2 > 0 ? 1.0 / (double)M2 : 0.0;
+        a.mod = mod; a.qrep = qrep;
+        a.roff = roff; a.rkey = rkey; a.done = done; a.moves = moves;
+        a.heavy_cnt = hcnt;
+        a.lvb = (unsigned long long*)I64(B_LVB, 2 * MSH);
+        FC_HIP(hipMemsetAsync(a.lvb, 0, 16 * MSH, c.stream));
+        a.mvt = (unsigned long long*)I64(B_MVT, nU0);
+        FC_HIP(hipMemsetAsync(a.mvt, 0, 8 * (size_t)nU0, c.stream));
     }
-    std::vector<int32_t> h_roff(n_r), h_rend(n_r);
-    for (int r = 0; r < n_r; ++r) { h_roff[r] = (int32_t)(r * N); h_rend[r] = (int32_t)((r + 1) * N); }
-    FC_HIP(hipMemcpyAsync(roff, h_roff.data(), 4 * (size_t)n_r, hipMemcpyHostToDevice, c.stream));
-    FC_HIP(hipMemcpyAsync(rend, h_rend.data(), 4 * (size_t)n_r, hipMemcpyHostToDevice, c.stream));
-    std::vector<uint8_t> h_done(n_r, 0);
-    uint32_t stamp_ctr = 0;
-    std::vector<uint32_t> h_rkey(n_r);
 
-    LvArgs a{};
-    a.N0 = N; a.M2 = M2; a.B = B;
-    a.inv = M2 > 0 ? 1.0 / (double)M2 : 0.0;
-    a.mod = mod; a.qrep = qrep;
-    a.roff = roff; a.rkey = rkey; a.done = done; a.moves = moves;
-    a.heavy_cnt = hcnt;
-    a.lvb = (unsigned long long*)I64(B_LVB, 2 * MSH);
-    FC_HIP(hipMemsetAsync(a.lvb, 0, 16 * MSH, c.stream));
-    a.mvt = (unsigned long long*)I64(B_MVT, nU0);
-    FC_HIP(hipMemsetAsync(a.mvt, 0, 8 * (size_t)nU0, c.stream));
-
-    LvGraph cur;            // explicit level (level >= 1)
-    int pp = 0;             // ping-pong slot of the next explicit level
-    int64_t nU = nU0;
-    bool impl = true;
-    int32_t max_deg = g.max_deg;
-
-    auto set_keys = [&](int level, int sweep, uint32_t salt) {
+    void set_keys(int level, int sweep, uint32_t salt) {
         for (int r = 0; r < n_r; ++r)
             h_rkey[r] = stream_key(c.seed, (uint32_t)(rbegin + r / tu), (uint32_t)iteration,
                                    (uint32_t)(level * 4096 + sweep), 16 + salt + 8 * (uint32_t)(trial0 + r % tu));
         FC_HIP(hipMemcpyAsync(rkey, h_rkey.data(), 4 * (size_t)n_r, hipMemcpyHostToDevice, c.stream));
-    };
-    auto set_graph = [&]() {
+    }
+
+    // the current level's graph, block lists and heavy lists into `a`
+    void bind_level() {
         a.nU = nU;
         if (impl) {
             a.rowptr = g.rowptr.as<int64_t>(); a.col = g.col.as<int32_t>();
@@ -1350,7 +1372,7 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
         // each length tier's list holds at most the level's rows past the smallest heavy
         // threshold (64 entries, k_lv_decide<.., 512, 4>), not nU each
         {
-            unsigned long long* dcnt = (unsigned long long*)(c.hpin + 48);
+            unsigned long long* dcnt = (unsigned long long*)(c.hpin + HP_LONG);
             unsigned long long* dd = (unsigned long long*)ensure<int64_t>(c.counters, 4);
             FC_HIP(hipMemsetAsync(dd, 0, 8, c.stream));
             const int64_t nrows = impl ? N : nU;
@@ -1366,9 +1388,10 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
         if (max_deg > HLIGHT)
             while (hs < 2 * (int64_t)max_deg) hs <<= 1;
         a.hslots = hs;
-    };
+    }
+
     // heavy-kernel grid: one global table per block, bounded to ~2 GB of tables
-    auto heavy_grid = [&](int64_t slots) {
+    int heavy_grid(int64_t slots) {
         int64_t gr = std::min<int64_t>(1024, std::max<int64_t>(1, ((int64_t)2 << 30) / (12 * slots)));
         const size_t need = (size_t)(gr * slots);
         const bool grow = c.lv[B_HKEY].bytes < need * 4 + 16;
@@ -1380,22 +1403,21 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
             FC_HIP(hipMemsetAsync(a.hval, 0, c.lv[B_HVAL].bytes, c.stream));
         }
         return (int)gr;
-    };
+    }
 
     // one bucketed sweep; returns moves
-    // Infomap passes: compacted bucket lists (FC_INFO_LISTS=0: every bucket launch scans the union)
-    static const bool info_lists = !getenv("FC_INFO_LISTS") || atoi(getenv("FC_INFO_LISTS")) != 0;
-    // rows of 65..128 entries: two vertices per wave (256 slots each), not one per wave
-    static const bool lv_g2 = !getenv("FC_LV_G2") || atoi(getenv("FC_LV_G2")) != 0;
-    std::vector<int32_t> h_icnt;
-    auto sweep = [&](int MODE, int level, int sw) -> unsigned long long {
-        set_keys(level, sw, (uint32_t)MODE);
+    unsigned long long sweep(int mode, int level, int sw) {
+        // Infomap passes: compacted bucket lists (FC_INFO_LISTS=0: every bucket launch scans the union)
+        static const bool info_lists = !getenv("FC_INFO_LISTS") || atoi(getenv("FC_INFO_LISTS")) != 0;
+        // rows of 65..128 entries: two vertices per wave (256 slots each), not one per wave
+        static const bool lv_g2 = !getenv("FC_LV_G2") || atoi(getenv("FC_LV_G2")) != 0;
+        set_keys(level, sw, (uint32_t)mode);
         FC_HIP(hipMemsetAsync(moves, 0, 8 * MSH, c.stream));
         int nblk = a.bmap ? a.bpr * a.nact : (int)nb(nU);
         const int hg = heavy_grid(a.hslots);
         const int hblk = 64;
         // Infomap: the pass's bucket lists (one host read of the B counts per pass)
-        const bool listed = MODE == MODE_INFO && info_lists && a.B <= ILIST_MAXB;
+        const bool listed = mode == MODE_INFO && info_lists && a.B <= ILIST_MAXB;
         int32_t* ill = nullptr;
         a.ilist = nullptr;
         if (listed) {
@@ -1406,12 +1428,10 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
             int32_t* ioff = ilc + nc + 1;
             int32_t* isz = ioff + nc + 1;
             ill = I32(B_ILL, nU);
-            if (impl) k_info_lcount<true><<<lblk, LTB, 0, c.stream>>>(a, span, ilc);
-            else k_info_lcount<false><<<lblk, LTB, 0, c.stream>>>(a, span, ilc);
+            dispatch(impl, [&](auto im) { k_info_lcount<im()><<<lblk, LTB, 0, c.stream>>>(a, span, ilc); });
             FC_HIP(hipMemsetAsync(ilc + nc, 0, sizeof(int32_t), c.stream));
             exclusive_scan(c, (const int32_t*)ilc, ioff, nc + 1);
-            if (impl) k_info_lfill<true><<<lblk, LTB, 0, c.stream>>>(a, span, ioff, ill);
-            else k_info_lfill<false><<<lblk, LTB, 0, c.stream>>>(a, span, ioff, ill);
+            dispatch(impl, [&](auto im) { k_info_lfill<im()><<<lblk, LTB, 0, c.stream>>>(a, span, ioff, ill); });
             k_info_lsizes<<<nb(a.B), LTB, 0, c.stream>>>(a.B, lblk, ioff, isz);
             h_icnt.resize(a.B);
             FC_HIP(hipMemcpyAsync(h_icnt.data(), isz, 4 * (size_t)a.B, hipMemcpyDeviceToHost, c.stream));
@@ -1430,45 +1450,24 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
             if (nblk == 0) continue;
             const uint32_t stamp = ++stamp_ctr;   // unique per bucket launch of this run (mvt)
             FC_HIP(hipMemsetAsync(hcnt, 0, 4 * NTIER, c.stream));
-            // (timed per launch into spans 5 / 6 when timing is on: lv decide / lv heavy)
-#define LV_LAUNCH(IM, MD)                                                                        \
-    do {                                                                                         \
-        const int t5 = timer_begin(c);                                                           \
-        if (max_deg <= 64) k_lv_decide<IM, MD, 512, 4><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);  \
-        else if (max_deg <= 128 && lv_g2) k_lv_decide<IM, MD, 512, 2><<<nblk, LTB, 0, c.stream>>>(a, b, stamp); \
-        else if (max_deg <= LWS_SMALL / 2) k_lv_decide<IM, MD, LWS_SMALL, 1><<<nblk, LTB, 0, c.stream>>>(a, b, stamp); \
-        else k_lv_decide<IM, MD, LWS, 1><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);               \
-        timer_end(c, 5, t5);                                                                     \
-        if (max_deg > LIGHT) {   /* tiers by row length (heavy_tier); tier 3: global tables */  \
-            /* one timer span per kernel launch, as rocprofv3 counts them */                     \
-            int t6 = timer_begin(c);                                                             \
-            k_lv_heavy<IM, MD, 2048><<<2048, LTB, 0, c.stream>>>(a, stamp, 0);                   \
-            timer_end(c, 6, t6);                                                                 \
-            if (max_deg > 1024) {                                                                \
-                t6 = timer_begin(c);                                                             \
-                k_lv_heavy<IM, MD, 4096><<<1280, LTB, 0, c.stream>>>(a, stamp, 1);               \
-                timer_end(c, 6, t6);                                                             \
-            }                                                                                    \
-            if (max_deg > 2048) {                                                                \
-                t6 = timer_begin(c);                                                             \
-                k_lv_heavy<IM, MD, HLS><<<512, LTB, 0, c.stream>>>(a, stamp, 2);                 \
-                timer_end(c, 6, t6);                                                             \
-            }                                                                                    \
-            if (max_deg > 4096) {                                                                \
-                t6 = timer_begin(c);                                                             \
-                k_lv_heavy<IM, MD, 2048><<<hg, LTB, 0, c.stream>>>(a, stamp, 3);                 \
-                timer_end(c, 6, t6);                                                             \
-            }                                                                                    \
-        }                                                                                        \
-        k_lv_apply<IM, MD><<<nblk + (max_deg > LIGHT ? hblk : 0), LTB, 0, c.stream>>>(a, nblk, hblk, stamp); \
-    } while (0)
-            if (impl && MODE == MODE_MOVE) LV_LAUNCH(true, MODE_MOVE);
-            else if (impl && MODE == MODE_REFINE) LV_LAUNCH(true, MODE_REFINE);
-            else if (impl) LV_LAUNCH(true, MODE_INFO);
-            else if (MODE == MODE_MOVE) LV_LAUNCH(false, MODE_MOVE);
-            else if (MODE == MODE_REFINE) LV_LAUNCH(false, MODE_REFINE);
-            else LV_LAUNCH(false, MODE_INFO);
-#undef LV_LAUNCH
+            dispatch(impl, mode, [&](auto im, auto md) {
+                constexpr bool IM = im();
+                constexpr int MD = md();
+                // (timed per launch into spans 5 / 6 when timing is on: lv decide / lv heavy)
+                const int t5 = timer_begin(c);
+                if (max_deg <= 64) k_lv_decide<IM, MD, 512, 4><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);
+                else if (max_deg <= 128 && lv_g2) k_lv_decide<IM, MD, 512, 2><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);
+                else if (max_deg <= LWS_SMALL / 2) k_lv_decide<IM, MD, LWS_SMALL, 1><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);
+                else k_lv_decide<IM, MD, LWS, 1><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);
+                timer_end(c, 5, t5);
+                if (max_deg > LIGHT)   // one timer span per kernel launch, as rocprofv3 counts them
+                    for_heavy_tiers(max_deg, hg, [&](auto hs, int grid, int tier) {
+                        const int t6 = timer_begin(c);
+                        k_lv_heavy<IM, MD, hs()><<<grid, LTB, 0, c.stream>>>(a, stamp, tier);
+                        timer_end(c, 6, t6);
+                    });
+                k_lv_apply<IM, MD><<<nblk + (max_deg > LIGHT ? hblk : 0), LTB, 0, c.stream>>>(a, nblk, hblk, stamp);
+            });
         }
         a.ilist = nullptr;
         std::vector<unsigned long long> hm(MSH);
@@ -1477,71 +1476,70 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
         unsigned long long t = 0;
         for (auto v : hm) t += v;
         return t;
-    };
+    }
 
-    int level = 0;
-    int64_t lv_sweeps = 0;
-    for (;; ++level) {
-        set_graph();
-        if (info) {
-            // ---- Infomap: greedy passes until one moves nothing (igraph: until the codelength
-            // stops improving; its tune() every 10 passes only refreshes float flows), then the
-            // modules are the units the level aggregates
-            a.P = P; a.mod = mod; a.qrep = qrep;
-            // a replica whose pass moved nothing is done at this level (re-sweeping it would
-            // move nothing again), so the trials and replicas still moving run alone
-            uint8_t* lvd = U8(B_LVDONE, n_r);
-            unsigned long long* rmv = (unsigned long long*)I64(B_RMOVES, n_r);
-            std::vector<uint8_t> h_lvd(h_done);
-            std::vector<unsigned long long> h_rmv(n_r);
-            FC_HIP(hipMemcpyAsync(lvd, h_lvd.data(), n_r, hipMemcpyHostToDevice, c.stream));
-            a.lvdone = lvd; a.rmoves = rmv;
-            a.bmap = nullptr;
-            for (int sw = 0; sw < c.max_sweeps; ++sw) {
-                ++lv_sweeps;
-                FC_HIP(hipMemsetAsync(rmv, 0, 8 * (size_t)n_r, c.stream));
-                if (c.trace && sw == 0) { sync(c); trace_dt_us(true); }
-                const unsigned long long mvs = sweep(MODE_INFO, level, sw);   // syncs
-                if (c.trace) {
-                    int na = 0;
-                    for (int r = 0; r < n_r; ++r) na += !h_lvd[r];
-                    fprintf(stderr, "[fc] infomap level %d pass %d: %d replicas, %llu moves, %.0f us\n", level, sw, na,
-                            mvs, trace_dt_us(false));
-                }
-                if (mvs == 0) break;
-                FC_HIP(hipMemcpy(h_rmv.data(), rmv, 8 * (size_t)n_r, hipMemcpyDeviceToHost));
-                for (int r = 0; r < n_r; ++r) h_lvd[r] |= h_rmv[r] == 0;
-                FC_HIP(hipMemcpyAsync(lvd, h_lvd.data(), n_r, hipMemcpyHostToDevice, c.stream));
-                if (impl) {   // the next passes launch blocks for the replicas still moving only
-                    std::vector<int32_t> act;
-                    for (int r = 0; r < n_r; ++r)
-                        if (!h_lvd[r]) act.push_back(r);
-                    if (act.empty()) { sync(c); break; }
-                    int32_t* bm = I32(B_BMAP, n_r);
-                    FC_HIP(hipMemcpyAsync(bm, act.data(), 4 * act.size(), hipMemcpyHostToDevice, c.stream));
-                    a.bmap = bm; a.nact = (int)act.size(); a.bpr = (int)nb(N);
-                    sync(c);   // `act` is pageable and local
-                }
-                sync(c);
-            }
-            a.bmap = nullptr;
-            a.R = R; a.rsize = rsize;
-            k_info_rclear<<<nb(nU), LTB, 0, c.stream>>>(nU, mod, rsize, rtot);
-            if (impl) k_info_modules<true><<<nb(nU), LTB, 0, c.stream>>>(a);
-            else k_info_modules<false><<<nb(nU), LTB, 0, c.stream>>>(a);
-            a.tot = rtot;
-        } else {
-            // ---- refine: singletons inside the move-phase communities, one sweep
-            if (!impl) k_lv_rinit<<<nb(nU), LTB, 0, c.stream>>>(nU, cur.kv, R, rtot, rsize);
-            a.P = P; a.R = R; a.tot = rtot; a.rsize = rsize;
-            sweep(MODE_REFINE, level, 0);
+    // Infomap: greedy passes until one moves nothing (igraph: until the codelength stops improving;
+    // its tune() every 10 passes only refreshes float flows), then the modules are the units the
+    // level aggregates
+    void infomap_passes(int level) {
+        a.P = P; a.mod = mod; a.qrep = qrep;
+        // a replica whose pass moved nothing is done at this level (re-sweeping it would
+        // move nothing again), so the trials and replicas still moving run alone
+        uint8_t* lvd = U8(B_LVDONE, n_r);
+        unsigned long long* rmv = (unsigned long long*)I64(B_RMOVES, n_r);
+        std::vector<uint8_t> h_lvd(h_done);
+        std::vector<unsigned long long> h_rmv(n_r);
+        FC_HIP(hipMemcpyAsync(lvd, h_lvd.data(), n_r, hipMemcpyHostToDevice, c.stream));
+        a.lvdone = lvd; a.rmoves = rmv;
+        a.bmap = nullptr;
+        for (int sw = 0; sw < c.max_sweeps; ++sw) {
             ++lv_sweeps;
+            FC_HIP(hipMemsetAsync(rmv, 0, 8 * (size_t)n_r, c.stream));
+            if (c.trace && sw == 0) { sync(c); trace_dt_us(true); }
+            const unsigned long long mvs = sweep(MODE_INFO, level, sw);   // syncs
+            if (c.trace) {
+                int na = 0;
+                for (int r = 0; r < n_r; ++r) na += !h_lvd[r];
+                fprintf(stderr, "[fc] infomap level %d pass %d: %d replicas, %llu moves, %.0f us\n", level, sw, na,
+                        mvs, trace_dt_us(false));
+            }
+            if (mvs == 0) break;
+            FC_HIP(hipMemcpy(h_rmv.data(), rmv, 8 * (size_t)n_r, hipMemcpyDeviceToHost));
+            for (int r = 0; r < n_r; ++r) h_lvd[r] |= h_rmv[r] == 0;
+            FC_HIP(hipMemcpyAsync(lvd, h_lvd.data(), n_r, hipMemcpyHostToDevice, c.stream));
+            if (impl) {   // the next passes launch blocks for the replicas still moving only
+                std::vector<int32_t> act;
+                for (int r = 0; r < n_r; ++r)
+                    if (!h_lvd[r]) act.push_back(r);
+                if (act.empty()) { sync(c); break; }
+                int32_t* bm = I32(B_BMAP, n_r);
+                FC_HIP(hipMemcpyAsync(bm, act.data(), 4 * act.size(), hipMemcpyHostToDevice, c.stream));
+                a.bmap = bm; a.nact = (int)act.size(); a.bpr = (int)nb(N);
+                sync(c);   // `act` is pageable and local
+            }
+            sync(c);
         }
-        // ---- which replicas still aggregate: refined communities < level nodes
-        int32_t* nid = I32(B_NID, nU + 1);
-        int32_t* fl = I32(B_FL, nU + 1);
-        if (impl) k_ag_flags<true><<<nb(nU + 1), LTB, 0, c.stream>>>(a, fl);
-        else k_ag_flags<false><<<nb(nU + 1), LTB, 0, c.stream>>>(a, fl);
+        a.bmap = nullptr;
+        a.R = R; a.rsize = rsize;
+        k_info_rclear<<<nb(nU), LTB, 0, c.stream>>>(nU, mod, rsize, rtot);
+        dispatch(impl, [&](auto im) { k_info_modules<im()><<<nb(nU), LTB, 0, c.stream>>>(a); });
+        a.tot = rtot;
+    }
+
+    // Leiden: singletons inside the move-phase communities, one sweep
+    void refine(int level) {
+        if (!impl) k_lv_rinit<<<nb(nU), LTB, 0, c.stream>>>(nU, cur.kv, R, rtot, rsize);
+        a.P = P; a.R = R; a.tot = rtot; a.rsize = rsize;
+        sweep(MODE_REFINE, level, 0);
+        ++lv_sweeps;
+    }
+
+    // A replica whose refined communities are its level's nodes is final: its labels go out.
+    // Returns whether any replica still aggregates; nid then numbers their refined communities.
+    bool finish_replicas(int level) {
+        nid = I32(B_NID, nU + 1);
+        fl = I32(B_FL, nU + 1);
+        dispatch(impl, [&](auto im) { k_ag_flags<im()><<<nb(nU + 1), LTB, 0, c.stream>>>(a, fl); });
         exclusive_scan(c, fl, nid, nU + 1);
         k_ag_counts<<<nb(n_r), LTB, 0, c.stream>>>(n_r, done, roff, rend, nid, misc);
         std::vector<int32_t> rc(n_r);
@@ -1555,7 +1553,7 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
             else any_left = true;
         }
         if (any_fin) {
-            uint8_t* dfin = (uint8_t*)(misc + n_r);
+            uint8_t* dfin = (uint8_t*)(misc + misc_fin(n_r));
             FC_HIP(hipMemcpyAsync(dfin, fin.data(), n_r, hipMemcpyHostToDevice, c.stream));
             if (info) k_info_codelen<<<n_r, LTB, 0, c.stream>>>(dfin, roff, rend, mod, qrep, a.inv, dcl);
             k_lv_final<<<nb(nU0), LTB, 0, c.stream>>>(N, n_r, dfin, memb, P, roff, c.spos.as<int32_t>(), lab_out);
@@ -1563,13 +1561,15 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
             FC_HIP(hipMemcpyAsync(done, h_done.data(), n_r, hipMemcpyHostToDevice, c.stream));
             sync(c);
         }
-        if (!any_left) break;
-        if (any_fin) {   // drop the finished replicas from the next level
-            if (impl) k_ag_flags<true><<<nb(nU + 1), LTB, 0, c.stream>>>(a, fl);
-            else k_ag_flags<false><<<nb(nU + 1), LTB, 0, c.stream>>>(a, fl);
+        if (any_left && any_fin) {   // drop the finished replicas from the next level
+            dispatch(impl, [&](auto im) { k_ag_flags<im()><<<nb(nU + 1), LTB, 0, c.stream>>>(a, fl); });
             exclusive_scan(c, fl, nid, nU + 1);
         }
-        // ---- aggregate by the refined partition
+        return any_left;
+    }
+
+    // the next level: the graph of the refined communities (Infomap: modules), which becomes `cur`
+    void aggregate(int level) {
         int64_t nUn = 0;
         {
             int32_t t32;
@@ -1585,28 +1585,24 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
         nx.rep = I32(gs + 4, nUn);
         nx.sv = info ? I64(gs + 5, nUn) : nullptr;
         int32_t* mcnt = I32(B_MCNT, nUn + 1);
-        if (impl) k_ag_nodes<true><<<nb(nU), LTB, 0, c.stream>>>(a, nid, nx.rep, nx.kv, mcnt, nx.sv);
-        else k_ag_nodes<false><<<nb(nU), LTB, 0, c.stream>>>(a, nid, nx.rep, nx.kv, mcnt, nx.sv);
+        dispatch(impl, [&](auto im) { k_ag_nodes<im()><<<nb(nU), LTB, 0, c.stream>>>(a, nid, nx.rep, nx.kv, mcnt, nx.sv); });
         FC_HIP(hipMemsetAsync(mcnt + nUn, 0, 4, c.stream));
         int32_t* moff = I32(B_MOFF, nUn + 1);
         exclusive_scan(c, mcnt, moff, nUn + 1);
-        int32_t* pofR = I32(B_HTGT, nU);   // free between sweeps
+        int32_t* pofR = I32(B_HTGT, nU);   // free between sweeps (bind_level takes them back)
         int32_t* prep = I32(B_HEAVY, nU);
         int64_t* ub = I64(B_UB, nUn + 1);
         int64_t* ubo = I64(B_UBO, nUn + 1);
         k_lv_fill_i32<<<nb(nU), LTB, 0, c.stream>>>(nU, prep, INT_MAX);
         FC_HIP(hipMemsetAsync(ub, 0, 8 * ((size_t)nUn + 1), c.stream));
-        if (impl) k_ag_members<true><<<nb(nU), LTB, 0, c.stream>>>(a, nid, pofR, prep, ub);
-        else k_ag_members<false><<<nb(nU), LTB, 0, c.stream>>>(a, nid, pofR, prep, ub);
+        dispatch(impl, [&](auto im) { k_ag_members<im()><<<nb(nU), LTB, 0, c.stream>>>(a, nid, pofR, prep, ub); });
         exclusive_scan(c, ub, ubo, nUn + 1);
         int32_t* mcur = I32(B_MCUR, nUn + 1);
         int32_t* mlist = I32(B_MLIST, nU + 1);
         FC_HIP(hipMemsetAsync(mcur, 0, 4 * (size_t)nUn, c.stream));
-        if (impl) k_ag_fill<true><<<nb(nU), LTB, 0, c.stream>>>(a, nid, moff, mcur, mlist);
-        else k_ag_fill<false><<<nb(nU), LTB, 0, c.stream>>>(a, nid, moff, mcur, mlist);
-        // [0] member-row sum total, [1] the longest one (bounds the heavy tables), [2] longest new row
-        int64_t* hx = (int64_t*)c.hpin + 40;
-        unsigned long long* dmax = (unsigned long long*)(misc + 2 * (int64_t)n_r + 2 + ((2 * n_r) & 1));
+        dispatch(impl, [&](auto im) { k_ag_fill<im()><<<nb(nU), LTB, 0, c.stream>>>(a, nid, moff, mcur, mlist); });
+        int64_t* hx = c.hpin + HP_AG;
+        unsigned long long* dmax = (unsigned long long*)(misc + misc_max(n_r));
         FC_HIP(hipMemsetAsync(dmax, 0, 16, c.stream));
         unsigned long long* dlong = (unsigned long long*)ensure<int64_t>(c.counters, 4);
         FC_HIP(hipMemsetAsync(dlong, 0, 8, c.stream));
@@ -1624,25 +1620,22 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
         int32_t* agh = I32(B_AGH, NTIER * ahc);
         FC_HIP(hipMemsetAsync(hcnt, 0, 4 * NTIER, c.stream));
         const unsigned agb = nb(nUn, LTB / 64);
-        if (impl) k_ag_rows<true><<<agb, LTB, 0, c.stream>>>(a, nUn, nid, moff, mlist, ubo, tcol, tw, olen, agh, hcnt, ahc);
-        else k_ag_rows<false><<<agb, LTB, 0, c.stream>>>(a, nUn, nid, moff, mlist, ubo, tcol, tw, olen, agh, hcnt, ahc);
+        dispatch(impl, [&](auto im) {
+            k_ag_rows<im()><<<agb, LTB, 0, c.stream>>>(a, nUn, nid, moff, mlist, ubo, tcol, tw, olen, agh, hcnt, ahc);
+        });
         if (ubmax > LIGHT) {
             int64_t hs = 64;
             if (ubmax > HLIGHT)
                 while (hs < 2 * ubmax) hs <<= 1;
             a.hslots = hs;
             const int hg = heavy_grid(hs);
-            // by length tier (heavy_tier): LDS tables sized for the tier, global tables past 4096
-#define AG_HEAVY(IM)                                                                                              \
-    do {                                                                                                          \
-        k_ag_rows_heavy<IM, 2048><<<2048, LTB, 0, c.stream>>>(a, nid, moff, mlist, ubo, tcol, tw, olen, agh, hcnt, ahc, 0); \
-        if (ubmax > 1024) k_ag_rows_heavy<IM, 4096><<<1280, LTB, 0, c.stream>>>(a, nid, moff, mlist, ubo, tcol, tw, olen, agh, hcnt, ahc, 1); \
-        if (ubmax > 2048) k_ag_rows_heavy<IM, HLS><<<512, LTB, 0, c.stream>>>(a, nid, moff, mlist, ubo, tcol, tw, olen, agh, hcnt, ahc, 2); \
-        if (ubmax > 4096) k_ag_rows_heavy<IM, 2048><<<hg, LTB, 0, c.stream>>>(a, nid, moff, mlist, ubo, tcol, tw, olen, agh, hcnt, ahc, 3); \
-    } while (0)
-            if (impl) AG_HEAVY(true);
-            else AG_HEAVY(false);
-#undef AG_HEAVY
+            dispatch(impl, [&](auto im) {
+                constexpr bool IM = im();
+                for_heavy_tiers(ubmax, hg, [&](auto slots, int grid, int tier) {
+                    k_ag_rows_heavy<IM, slots()><<<grid, LTB, 0, c.stream>>>(a, nid, moff, mlist, ubo, tcol, tw, olen,
+                                                                            agh, hcnt, ahc, tier);
+                });
+            });
         }
         int64_t* len64 = I64(B_LEN64, nUn + 1);
         k_ag_len64<<<nb(nUn + 1), LTB, 0, c.stream>>>(nUn, olen, len64);
@@ -1672,25 +1665,27 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
         impl = false;
         nU = nUn;
         max_deg = nx.max_deg;
-        if (info) {   // singleton modules of the aggregate nodes; the next loop trip optimises them
-            mod = I64(B_POUT, 2 * nU);
-            R = I32(B_R, nU); rtot = I64(B_RTOT, nU); rsize = I32(B_RSIZE, nU);
-            k_info_level<<<nb(nU), LTB, 0, c.stream>>>(nU, cur.kv, cur.sv, mod);
-            if (c.trace) {
-                sync(c);
-                fprintf(stderr, "[fc] infomap level %d: %lld union vertices, %lld entries, max degree %d\n", level + 1,
-                        (long long)nU, (long long)cur.E, max_deg);
-            }
-            continue;
+        if (!info) return;   // Leiden goes on with move_phase()
+        // singleton modules of the aggregate nodes; the next loop trip optimises them
+        mod = I64(B_POUT, 2 * nU);
+        R = I32(B_R, nU); rtot = I64(B_RTOT, nU); rsize = I32(B_RSIZE, nU);
+        k_info_level<<<nb(nU), LTB, 0, c.stream>>>(nU, cur.kv, cur.sv, mod);
+        if (c.trace) {
+            sync(c);
+            fprintf(stderr, "[fc] infomap level %d: %lld union vertices, %lld entries, max degree %d\n", level + 1,
+                    (long long)nU, (long long)cur.E, max_deg);
         }
-        // ---- move phase on the new level, from the inherited partition, until no move
+    }
+
+    // Leiden: move phase on the level aggregate() built, from the inherited partition, until no move
+    void move_phase(int level) {
         ptot = I64(B_PTOT, nU);
         R = I32(B_R, nU); rtot = I64(B_RTOT, nU); rsize = I32(B_RSIZE, nU);
         FC_HIP(hipMemsetAsync(ptot, 0, 8 * (size_t)nU, c.stream));
         k_ag_ptot<<<nb(nU), LTB, 0, c.stream>>>(nU, P, cur.kv, ptot);
         uint8_t* act = U8(B_ACT, nU);
         k_lv_fill_u8<<<nb(nU), LTB, 0, c.stream>>>(nU, act, done, cur.rep);
-        set_graph();
+        bind_level();
         a.P = P; a.R = R; a.tot = ptot; a.rsize = rsize; a.act = act;
         // aggregate levels: lv_level_b buckets per move sweep (default 4, not level 0's 32).  The
         // dense levels run tens of sweeps whose queues are a few re-queued vertices per replica;
@@ -1716,8 +1711,6 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
                 FC_HIP(hipMemcpy(hb.data(), a.lvb, 16 * MSH, hipMemcpyDeviceToHost));
                 unsigned long long bd = 0, bh = 0;
                 for (int k = 0; k < MSH; ++k) { bd += hb[k]; bh += hb[MSH + k]; }
-                static unsigned long long pd = 0, ph = 0;
-                if (bd < pd || bh < ph) pd = ph = 0;
                 fprintf(stderr, "[fc] leiden level %d sweep %d: %llu moves, %.2f ms, decide %.1f MB, heavy %.1f MB\n",
                         level + 1, sw, mvs,
                         1e-3 * (double)std::chrono::duration_cast<std::chrono::microseconds>(
@@ -1734,19 +1727,67 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
                     1e-3 * trace_dt_us());
         }
     }
-    if (c.trace) fprintf(stderr, "[fc] %s it=%d: %d levels, %lld level sweeps\n", name, iteration, level + 1,
-                         (long long)lv_sweeps);
-    if (info) FC_HIP(hipMemcpyAsync(cl_out, dcl, 8 * (size_t)n_r, hipMemcpyDeviceToHost, c.stream));
-    std::vector<unsigned long long> lvb(2 * MSH);
-    FC_HIP(hipMemcpyAsync(lvb.data(), a.lvb, 16 * MSH, hipMemcpyDeviceToHost, c.stream));
-    sync(c);
-    unsigned long long lvd = 0, lvh = 0;
-    for (int k = 0; k < MSH; ++k) { lvd += lvb[k]; lvh += lvb[MSH + k]; }
-    for (fc_stats* st : {&c.acc, &c.prof}) {
-        st->cd_sweeps += lv_sweeps * n_r;
-        st->lv_decide_bytes += (int64_t)lvd;
-        st->lv_heavy_bytes += (int64_t)lvh;
+
+    // codelengths out (Infomap), sweep and algorithmic-byte statistics
+    void statistics(int levels, double* cl_out) {
+        if (c.trace) fprintf(stderr, "[fc] %s it=%d: %d levels, %lld level sweeps\n", info ? "infomap" : "leiden",
+                             iteration, levels, (long long)lv_sweeps);
+        if (info) FC_HIP(hipMemcpyAsync(cl_out, dcl, 8 * (size_t)n_r, hipMemcpyDeviceToHost, c.stream));
+        std::vector<unsigned long long> lvb(2 * MSH);
+        FC_HIP(hipMemcpyAsync(lvb.data(), a.lvb, 16 * MSH, hipMemcpyDeviceToHost, c.stream));
+        sync(c);
+        unsigned long long lvd = 0, lvh = 0;
+        for (int k = 0; k < MSH; ++k) { lvd += lvb[k]; lvh += lvb[MSH + k]; }
+        for (fc_stats* st : {&c.acc, &c.prof}) {
+            st->cd_sweeps += lv_sweeps * n_r;
+            st->lv_decide_bytes += (int64_t)lvd;
+            st->lv_heavy_bytes += (int64_t)lvh;
+        }
     }
+};
+
+}  // namespace
+
+// One multi-level run per local replica on the working graph c.g; labels -> lab_out (slot
+// order, values in [0, N) per replica), exactly like cd_run leaves c.lab.
+//   info = false: Leiden (level-0 move on the Louvain engine, refine, aggregate by R);
+//   info = true:  `tu` Infomap trials per replica side by side in the union (union replica
+//                 u = r*tu + j runs trial trial0 + j of replica r: the same random streams as
+//                 running the trials one after the other); map-equation passes at every
+//                 level, aggregation by the modules; cl_out[u] = its codelength (without the
+//                 constant node-entropy term) for the best-of-trials choice.
+static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total, int iteration, int tu, int trial0,
+                       int32_t* lab_out, double* cl_out) {
+    FC_REQUIRE(rcount >= 1 && rbegin >= 0 && rbegin + rcount <= n_p_total, FC_EINVAL, "bad replica range");
+    FC_REQUIRE(c.N > 0 && c.g.rowptr.p, FC_ESTATE, "no graph loaded");
+    // Infomap runs on the topology (community_infomap() without weights, :268 / :390)
+    const int64_t M2 = info ? 2 * c.g.m : c.g.M2;
+    FC_REQUIRE(M2 < 0x7fffffffll, FC_ELIMIT, "leiden/infomap: total edge weight must stay below 2^30");
+    FC_REQUIRE(tu >= 1 && (info || tu == 1), FC_EINVAL, "trials side by side are for Infomap");
+    FC_REQUIRE((int64_t)rcount * tu * c.N < 0x7fffffffll, FC_ELIMIT,
+               "leiden/infomap: replicas x trials x nodes must stay below 2^31");
+
+    if (!info) {
+        // ---- level 0, move phase: the replica-batched local-moving engine run to exhaustion
+        RestoreMinDq restore{c, c.cd_min_dq};
+        c.cd_min_dq = 0.0;
+        cd_run(c, FC_ALGO_LOUVAIN, rbegin, rcount, n_p_total, iteration);
+    }
+    // lab_out == nullptr: c.lab, read only now (cd_run above may have (re)allocated it)
+    if (!lab_out) lab_out = ensure<int32_t>(c.lab, (size_t)rcount * (size_t)c.N);
+    const int sl0 = timer_begin(c);   // (cd_run timed itself) refinement, Infomap passes and the levels
+
+    LvRun run(c, info, rbegin, rcount, iteration, tu, trial0, M2, lab_out);
+    int level = 0;
+    for (;; ++level) {
+        run.bind_level();
+        if (info) run.infomap_passes(level);
+        else run.refine(level);
+        if (!run.finish_replicas(level)) break;   // every replica has its final labels
+        run.aggregate(level);
+        if (!info) run.move_phase(level);
+    }
+    run.statistics(level + 1, cl_out);
     c.n_r = rcount; c.rbase = rbegin; c.n_p_total = n_p_total;
     c.labT_valid = false;
     timer_end(c, 0, sl0);
