@@ -32,6 +32,7 @@ SYMBOLS = [
     "fc_generate_lfr", "fc_generate_sbm", "fc_read_edgelist",
     "fc_score_set_reference", "fc_score_partitions", "fc_score_pairs",
     "fc_consensus_support", "fc_consensus_partition", "fc_consensus_timing",
+    "fc_consensus_levels", "fc_consensus_cut", "fc_consensus_levels_timing",
 ]
 FC_SCORE_REF = -1
 SCORE_GRAPHS = {"input": 0, "working": 1}
@@ -89,6 +90,15 @@ class ConsensusInfo(ctypes.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class LevelScore(ctypes.Structure):
+    """fc_level_score"""
+    _fields_ = [
+        ("bucket_edges", ctypes.c_int64), ("k", ctypes.c_int64), ("max_size", ctypes.c_int64),
+        ("singletons", ctypes.c_int64), ("in_weight", ctypes.c_int64), ("tot_sq_lo", ctypes.c_uint64),
+        ("tot_sq_hi", ctypes.c_uint64), ("modularity", ctypes.c_double),
+    ]
 
 
 _lib = None
@@ -151,6 +161,10 @@ def load():
     # graph, dev_support or NULL, n_total, agreement, labels, hist, node_in, node_out, fc_consensus_info
     L.fc_consensus_partition.argtypes = [vp, c_int, vp, c_int, dbl, vp, vp, vp, vp, vp]
     L.fc_consensus_timing.argtypes = [vp, P(dbl)]
+    # graph, dev_support or NULL, n_total, birth, up, fc_level_score[n_total + 1], best_level
+    L.fc_consensus_levels.argtypes = [vp, c_int, vp, c_int, vp, vp, vp, P(i32)]
+    L.fc_consensus_cut.argtypes = [vp, c_int, vp, P(i64)]
+    L.fc_consensus_levels_timing.argtypes = [vp, P(dbl)]
     _lib = L
     return L
 

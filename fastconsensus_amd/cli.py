@@ -6,13 +6,16 @@ Same flags, defaults, validation messages and exit status, same output tree:
 ``--seed`` (the reference is unseeded), ``--device`` and ``--consensus THETA``, which also writes
 the consensus partition (``Engine.consensus_partition``) to ``consensus_t.../partition`` (one
 community per line) and ``consensus_t.../membership`` (``node+1<TAB>community+1``, sorted by node).
+``--consensus-levels`` picks the threshold itself (``Engine.consensus_levels``): the same two
+files hold the level of largest modularity, and ``consensus_t.../levels.tsv`` one row per level.
 """
 import argparse
 import os
 import sys
 
 from ._lib import FC_ALGO_LOUVAIN, FC_ALGO_LOUVAIN_NC
-from .core import ALGORITHMS, OUT_OF_SCOPE, RULES, Engine, IdGraph, algo_id, labels_to_output
+from .core import (ALGORITHMS, OUT_OF_SCOPE, RULES, Engine, IdGraph, algo_id, best_consensus, labels_to_output,
+                   theta_of)
 
 DEFAULT_TAU = {'louvain': 0.2, 'cnm': 0.7, 'infomap': 0.6, 'lpm': 0.8}   # :426
 
@@ -51,6 +54,8 @@ def build_parser():
     p.add_argument('--rule', type=str, default='fast_consensus', choices=RULES, help=argparse.SUPPRESS)
     # extension: also write the consensus partition at this agreement threshold
     p.add_argument('--consensus', type=float, default=None, help=argparse.SUPPRESS)
+    # extension: the consensus hierarchy; writes every level's record and the best level's partition
+    p.add_argument('--consensus-levels', action='store_true', help=argparse.SUPPRESS)
     return p
 
 
@@ -101,6 +106,20 @@ def write_consensus(args, node_labels, labels, root='.'):
             f.write(str(k + 1) + "\t" + str(v + 1) + '\n')
 
 
+def write_levels(args, node_labels, levels, labels, root='.'):
+    """consensus_t.../levels.tsv beside the best level's partition and membership
+    (write_consensus): one row per level 0..n_total, no header, the columns level, theta,
+    bucket_edges, k, max_size, singletons, modularity.  levels: the structured array of
+    Engine.consensus_levels."""
+    write_consensus(args, node_labels, labels, root=root)
+    d = os.path.join(root, 'consensus_' + output_dirs(args)[0][len('out_partitions_'):])
+    cols = ('bucket_edges', 'k', 'max_size', 'singletons')
+    with open(os.path.join(d, 'levels.tsv'), 'w') as f:
+        for s, r in enumerate(levels):
+            f.write("\t".join([str(s), repr(theta_of(s, len(levels) - 1))] + [str(int(r[c])) for c in cols]
+                              + [repr(float(r['modularity']))]) + '\n')
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.t is None:
@@ -109,6 +128,8 @@ def main(argv=None):
         sys.exit(0)                               # quit() -> exit status 0 (:430-432)
     if args.consensus is not None and not 0 <= args.consensus <= 1:
         raise SystemExit("--consensus must lie in [0, 1]")
+    if args.consensus is not None and args.consensus_levels:
+        raise SystemExit("--consensus and --consensus-levels both write the consensus partition: give one")
     cons = None
     g = IdGraph.from_edgelist_file(args.f)
     algo = algo_id(args.alg)
@@ -122,11 +143,15 @@ def main(argv=None):
             labels, _ = eng.run(algo, args.np, args.t, args.d)
             if args.consensus is not None:
                 cons = eng.consensus_partition(args.consensus)
+            if args.consensus_levels:
+                cons = best_consensus(eng)
         output = labels_to_output(args.alg, g.labels, labels)
     if output is None:                            # reference: TypeError on len(None)
         raise SystemExit("fast_consensus returned None")
     write_outputs(args, output)
-    if cons is not None:
+    if cons is not None and args.consensus_levels:
+        write_levels(args, g.labels, cons["levels"], cons["labels"])
+    elif cons is not None:
         write_consensus(args, g.labels, cons["labels"])
 
 

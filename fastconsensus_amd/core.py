@@ -356,6 +356,18 @@ class Engine:
         _, m, m0 = self.graph_info()
         return m0 if graph == "input" else m
 
+    def _support_total(self, graph, dev_support, n_total):
+        """n_total of a consensus call: the local replica count, or the caller's with a checked
+        `dev_support`."""
+        m = self._graph_edges(graph)
+        if dev_support is None:
+            return self.replica_info()[0]
+        if n_total is None:
+            raise ValueError("dev_support needs n_total, the number of replicas it was summed over")
+        if dev_support.dtype != torch_int32() or dev_support.numel() < m:
+            raise ValueError("dev_support must be an int32 tensor of >= %d elements" % m)
+        return int(n_total)
+
     def consensus_support(self, graph="input", dev_out=None):
         """Per edge of `graph`, the number of local labelings that put both ends in one community:
         an int32 device tensor [m] in the engine's edge order (consensus_partial's; the same on
@@ -381,15 +393,7 @@ class Engine:
         node_in / (node_in + node_out) (1.0 for a node without support), and the
         fc_consensus_info fields (edges, kept_edges, unanimous_edges, split_edges, k, max_size,
         singletons, n_total, passes, cut)."""
-        m = self._graph_edges(graph)
-        if dev_support is None:
-            nt = self.replica_info()[0]
-        else:
-            if n_total is None:
-                raise ValueError("dev_support needs n_total, the number of replicas it was summed over")
-            if dev_support.dtype != torch_int32() or dev_support.numel() < m:
-                raise ValueError("dev_support must be an int32 tensor of >= %d elements" % m)
-            nt = int(n_total)
+        nt = self._support_total(graph, dev_support, n_total)
         n = self.n
         labels = np.empty(n, np.int32)
         hist = np.zeros(max(nt, 0) + 1, np.int64)
@@ -410,6 +414,41 @@ class Engine:
         ms = (ctypes.c_double * 5)()
         check(self._L.fc_consensus_timing(self._ctx, ms))
         return dict(zip(("support", "histogram", "components", "renumber", "node_sums"), ms))
+
+    # -- the consensus hierarchy (fc_consensus_levels / fc_consensus_cut) ------------------
+    def consensus_levels(self, graph="input", dev_support=None, n_total=None):
+        """Every agreement level at once: level s (0..n_total) is the connected components of
+        the edges of `graph` with support >= s.  `dev_support` / `n_total` as in
+        consensus_partition.  Returns a dict: birth, up int32[n] (the tree: cut_tree(birth, up, s)
+        gives level s without an engine), levels (a structured array [n_total + 1] with
+        bucket_edges, k, max_size, singletons, in_weight, tot_sq_lo, tot_sq_hi, modularity),
+        best_level (the level of largest modularity, compared as exact integers; the highest
+        among equals), best_theta = theta_of(best_level, n_total) and n_total.  The tree stays in
+        the engine for consensus_cut."""
+        nt = self._support_total(graph, dev_support, n_total)
+        n = self.n
+        birth = np.empty(n, np.int32)
+        up = np.empty(n, np.int32)
+        levels = np.zeros(max(nt, 0) + 1, LEVEL_DTYPE)
+        best = ctypes.c_int32()
+        check(self._L.fc_consensus_levels(self._ctx, _lib.SCORE_GRAPHS[graph], self._dev(dev_support), nt,
+                                          ptr(birth), ptr(up), ptr(levels), ctypes.byref(best)))
+        return {"birth": birth, "up": up, "levels": levels, "best_level": best.value,
+                "best_theta": theta_of(best.value, nt), "n_total": nt}
+
+    def consensus_cut(self, level):
+        """(labels int32[n] in node order, k) of level `level` of the last consensus_levels."""
+        labels = np.empty(self.n, np.int32)
+        k = ctypes.c_int64()
+        check(self._L.fc_consensus_cut(self._ctx, int(level), ptr(labels), ctypes.byref(k)))
+        return labels, k.value
+
+    def consensus_levels_timing(self):
+        """Device milliseconds of the phases of the last consensus_levels made with timing on
+        (set_timing): bucket, tree, statistics, join_levels."""
+        ms = (ctypes.c_double * 4)()
+        check(self._L.fc_consensus_levels_timing(self._ctx, ms))
+        return dict(zip(("bucket", "tree", "statistics", "join_levels"), ms))
 
     def nmi_matrix(self):
         """Symmetric [n_r, n_r] float64 NMI between the local replicas (unit diagonal)."""
@@ -433,6 +472,40 @@ PAIR_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.PairScore._fields_], al
 assert PART_DTYPE.itemsize == ctypes.sizeof(_lib.PartScore) and PAIR_DTYPE.itemsize == ctypes.sizeof(_lib.PairScore)
 CONSENSUS_INFO_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.ConsensusInfo._fields_], align=True)
 assert CONSENSUS_INFO_DTYPE.itemsize == ctypes.sizeof(_lib.ConsensusInfo)
+LEVEL_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.LevelScore._fields_], align=True)
+assert LEVEL_DTYPE.itemsize == ctypes.sizeof(_lib.LevelScore)
+
+
+def level_of(theta, n_total):
+    """The level a threshold selects: the smallest integer s that the float64 keep rule keeps,
+    i.e. with not (float(s) < theta * float(n_total)).  Scalars or arrays."""
+    cut = np.asarray(theta, np.float64) * np.asarray(n_total, np.float64)
+    s = np.maximum(np.ceil(cut), 0.0)           # ceil of a float64 is exact: float(s) >= cut, float(s - 1) < cut
+    return s.astype(np.int64) if s.ndim else int(s)
+
+
+def theta_of(level, n_total):
+    """A threshold that selects `level`: (level - 0.5) / n_total, and 0.0 for level 0, so that
+    level_of(theta_of(s, n_total), n_total) == s.  Scalars or arrays."""
+    level = np.asarray(level, np.float64)
+    t = np.where(level >= 1, (level - 0.5) / np.asarray(n_total, np.float64), 0.0)
+    return t if t.ndim else float(t)
+
+
+def cut_tree(birth, up, level):
+    """Labels int32[n] of level `level` from a consensus_levels tree, by pointer jumping in
+    numpy: the same labels as Engine.consensus_cut(level)."""
+    birth = np.asarray(birth)
+    n = len(birth)
+    idx = np.arange(n, dtype=np.int64)
+    nxt = np.where(birth >= level, np.asarray(up, np.int64), idx)    # one step, or stay at root_level
+    while True:
+        jump = nxt[nxt]
+        if np.array_equal(jump, nxt):
+            break
+        nxt = jump
+    rank = np.cumsum(nxt == idx) - 1
+    return rank[nxt].astype(np.int32)
 
 
 def stability(node_in, node_out):
@@ -442,6 +515,19 @@ def stability(node_in, node_out):
     nz = tot != 0
     out[nz] = node_in[nz] / tot[nz]
     return out
+
+
+def best_consensus(eng, dev_support=None, n_total=None):
+    """consensus="best": the hierarchy (consensus_levels), then the consensus partition at the
+    best level's threshold -- every field consensus_partition returns, plus level, theta, levels,
+    birth and up.  dev_support: the support summed over n_total replicas (the sharded driver's);
+    None: both calls count it over the engine's own labelings, which keeps the one-engine paths
+    (fast_consensus, the command line) free of torch, as with a float threshold."""
+    lev = eng.consensus_levels("input", dev_support=dev_support, n_total=n_total)
+    cons = eng.consensus_partition(lev["best_theta"], "input", dev_support=dev_support, n_total=n_total)
+    cons.update(level=lev["best_level"], theta=lev["best_theta"], levels=lev["levels"], birth=lev["birth"],
+                up=lev["up"])
+    return cons
 
 
 def consensus_scores(eng, sc, cons, truth=None):
@@ -791,7 +877,15 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     With ``scores=True`` as well, ``scores`` gains ``nmi_consensus[n_p]`` and
     ``ari_consensus[n_p]`` (every partition against the consensus partition),
     ``consensus_modularity`` and, with ``truth``, ``consensus_nmi_truth`` / ``consensus_ari_truth``.
+
+    ``consensus="best"`` picks the threshold itself: the consensus hierarchy over all levels
+    0..n_p (``Engine.consensus_levels``) and the consensus partition at the level of largest
+    modularity on G (the strictest among equals).  The ``consensus`` dict then also holds
+    ``level``, ``theta``, ``levels`` (one record per level), ``birth`` and ``up`` (the tree:
+    ``cut_tree(birth, up, s)`` gives any other level).
     """
+    if isinstance(consensus, str) and consensus != "best":
+        raise ValueError('consensus must be a threshold in [0, 1] or "best"')
     algo = algo_id(algorithm)
     if algo is None:
         return None
@@ -814,7 +908,10 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
         eng.load_graph(g.n, g.u, g.v)
         labels, stats = eng.run(algo, int(n_p), float(thresh), float(delta))
         tr = None if truth is None else truth_array(truth, g.labels)
-        cons = eng.consensus_partition(float(consensus)) if consensus is not None else None
+        if isinstance(consensus, str):
+            cons = best_consensus(eng)
+        else:
+            cons = eng.consensus_partition(float(consensus)) if consensus is not None else None
         sc = run_scores(eng, tr) if scores else None
         if cons is not None and scores:
             consensus_scores(eng, sc, cons, tr)

@@ -156,7 +156,8 @@ void fc_destroy(fc_ctx* ctx) {
                       &c.nodetmp3, &c.part, &c.ccount, &c.tailbuf, &c.tailmark, &c.sigma, &c.npos, &c.spos, &c.sinv, &c.tpos, &c.snpos, &c.st_u, &c.st_v, &c.st_w, &c.st_age,
                       &c.st_lab, &c.clo_rec, &c.clo_hkey, &c.clo_hval, &c.clo_list, &c.clo_cnt, &c.clo_akey, &c.clo_aval, &c.clo_rowptr, &c.clo_col, &c.clo_rowptr2, &c.clo_col2, &c.clo_nrow, &c.clo_ncol, &c.clo_own, &c.clo_own2, &c.mvf,
                       &c.sc_ref, &c.sc_key, &c.sc_val, &c.sc_ulab, &c.sc_cnt, &c.sc_nruns, &c.sc_seg, &c.sc_kd, &c.sc_kp, &c.sc_part, &c.sc_part2, &c.sc_res, &c.sc_want, &c.sc_ovf, &c.sc_e1, &c.sc_e2, &c.sc_fk1, &c.sc_fk2, &c.sc_fcnt, &c.sc_rng,
-                      &c.cp_sup, &c.cp_parent, &c.cp_flag, &c.cp_rank, &c.cp_lab, &c.cp_labi, &c.cp_size, &c.cp_hist, &c.cp_nin, &c.cp_nout};
+                      &c.cp_sup, &c.cp_parent, &c.cp_flag, &c.cp_rank, &c.cp_lab, &c.cp_labi, &c.cp_size, &c.cp_hist, &c.cp_nin, &c.cp_nout,
+                      &c.lv_birth, &c.lv_up, &c.lv_cursor, &c.lv_bucket, &c.lv_tot, &c.lv_stats, &c.lv_fold, &c.lv_jw};
     for (auto* b : bufs) b->release();
     for (auto e : c.timer.pool) (void)hipEventDestroy(e);
     for (auto e : c.sweep_ev) (void)hipEventDestroy(e);
@@ -232,6 +233,7 @@ int fc_load_graph(fc_ctx* ctx, int64_t n, int64_t m, const int32_t* u, const int
     graph_load(c, n, m, u, v);
     c.n_r = 0;
     c.sc_ref_set = false;   // a reference labeling belongs to the graph it was set on
+    c.lv_valid = false;     // and so does a consensus hierarchy
     FC_API_END
 }
 
@@ -533,6 +535,37 @@ int fc_consensus_timing(fc_ctx* ctx, double* ms) {
     FC_API_BEGIN
     FC_REQUIRE(ms, FC_EINVAL, "null output buffer");
     for (int i = 0; i < CP_PHASES; ++i) ms[i] = c.cp_ms[i];
+    FC_API_END
+}
+
+int fc_consensus_levels(fc_ctx* ctx, int graph, const void* dev_support, int n_total, int32_t* birth, int32_t* up,
+                        fc_level_score* levels, int32_t* best_level) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    FC_REQUIRE(!dev_support || n_total >= 1, FC_EINVAL, "reduced support needs n_total >= 1");
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(dev_support || c.n_r > 0, FC_ESTATE,
+               "no labelings and no support: run fc_run, fc_cd or fc_set_labels first, or pass dev_support");
+    consensus_levels(c, graph, (const int32_t*)dev_support, n_total, birth, up, levels, best_level);
+    FC_API_END
+}
+
+int fc_consensus_cut(fc_ctx* ctx, int level, int32_t* labels_out, int64_t* k_out) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(c.N > 0 && c.lv_valid, FC_ESTATE, "no consensus hierarchy: call fc_consensus_levels first");
+    FC_REQUIRE(level >= 0 && level <= c.lv_nt, FC_EINVAL,
+               "level " + std::to_string(level) + " outside [0, " + std::to_string(c.lv_nt) + "]");
+    consensus_cut(c, level, labels_out, k_out);
+    FC_API_END
+}
+
+int fc_consensus_levels_timing(fc_ctx* ctx, double* ms) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(ms, FC_EINVAL, "null output buffer");
+    for (int i = 0; i < LV_PHASES; ++i) ms[i] = c.lv_ms[i];
     FC_API_END
 }
 

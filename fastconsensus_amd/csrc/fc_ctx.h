@@ -245,6 +245,14 @@ struct Ctx {
     // renumber + sizes, node sums
     double cp_ms[5] = {0, 0, 0, 0, 0};
     DevBuf cp_sup, cp_parent, cp_flag, cp_rank, cp_lab, cp_labi, cp_size, cp_hist, cp_nin, cp_nout;
+    // consensus hierarchy (levels.h): the tree of the last successful fc_consensus_levels (birth, up
+    // by node; lv_valid until the next fc_load_graph) and its scratch: slice cursors, edge ids by
+    // support, degree sums by root, sharded per-level counters and their fold, join-level weights
+    // device time of the last call's phases (timing enabled): bucket, tree, statistics, join levels
+    double lv_ms[4] = {0, 0, 0, 0};
+    DevBuf lv_birth, lv_up, lv_cursor, lv_bucket, lv_tot, lv_stats, lv_fold, lv_jw;
+    bool lv_valid = false;
+    int lv_nt = 0;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = getenv("FC_SCORE_SLOW") ? atoi(getenv("FC_SCORE_SLOW")) : 0;
     // longest community one wave streams; longer ones go to the fallback
@@ -255,6 +263,7 @@ struct Ctx {
 
 struct Ctx;
 constexpr int CP_PHASES = 5;        // Ctx::cp_ms
+constexpr int LV_PHASES = 4;        // Ctx::lv_ms
 constexpr int FC_HPIN_I64 = 2048;   // pinned host scratch: per-sweep records (cd_rl.hip: boff | voff | n_active)
 // State the replica-lane engine hands to cd_run at the first filtered sweep of a hybrid batch
 // (FC_OPT_CD_ENGINE=2, cd_rl.hip): fill() writes it in cd.hip's layout on c.stream -- labels
@@ -343,6 +352,10 @@ void consensus_support(Ctx& c, int graph, int32_t* dev_out);
 void consensus_partition(Ctx& c, int graph, const int32_t* dev_support, int n_total, double agreement,
                          int32_t* labels_out, int64_t* hist_out, int64_t* nin_out, int64_t* nout_out,
                          fc_consensus_info* info);
+// levels.h (in consensus.hip): arguments validated by the caller
+void consensus_levels(Ctx& c, int graph, const int32_t* dev_support, int n_total, int32_t* birth_out, int32_t* up_out,
+                      fc_level_score* levels_out, int32_t* best_out);
+void consensus_cut(Ctx& c, int level, int32_t* labels_out, int64_t* k_out);
 // timing helpers
 int timer_begin(Ctx& c);
 void timer_end(Ctx& c, int slot, int begin_ev);

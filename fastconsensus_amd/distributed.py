@@ -141,12 +141,17 @@ class SharedOutput:
 def _consensus(engine, theta, n_p, world, mine, device):
     """The consensus partition of the run's n_p final partitions, replicated: every rank counts
     the support of the input graph's edges over ITS replicas, one SUM all-reduce adds them, and
-    every rank takes the components of the agreeing edges (identical on every rank)."""
+    every rank takes the components of the agreeing edges (identical on every rank).  theta
+    "best": the hierarchy over the reduced support and the partition at its best level
+    (core.best_consensus), again the same on every rank."""
     _, _, m0 = engine.graph_info()
     sup = torch.zeros(max(m0, 1), dtype=torch.int32, device=device)
     if mine > 0:
         engine.consensus_support("input", sup)
     _all_reduce_small(sup, dist.ReduceOp.SUM, n_p, world, 0)
+    if isinstance(theta, str):
+        from .core import best_consensus
+        return best_consensus(engine, sup, n_p)
     return engine.consensus_partition(theta, "input", dev_support=sup, n_total=n_p)
 
 
@@ -165,7 +170,11 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     writes its own rows, rank 0 returns it once all have.
     consensus: an agreement threshold in [0, 1]; the return value is then (labels, stats,
     consensus) with the dict of Engine.consensus_partition over all n_p final partitions on the
-    input graph, the same on every rank."""
+    input graph, the same on every rank.  consensus="best": the threshold is chosen by the
+    consensus hierarchy (Engine.consensus_levels over the reduced support); the dict then also
+    holds level, theta, levels, birth and up."""
+    if isinstance(consensus, str) and consensus != "best":
+        raise ValueError('consensus must be a threshold in [0, 1] or "best"')
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
     if out_shared and world > 1 and out is None:
@@ -247,7 +256,8 @@ def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank,
     if mine > 0:
         engine.cd(algo, r0, mine, n_p, FINAL_PASS_ITER + it)         # final pass :383-392
     if consensus is not None:
-        st["consensus"] = _consensus(engine, float(consensus), n_p, world, mine, device)
+        st["consensus"] = _consensus(engine, consensus if isinstance(consensus, str) else float(consensus), n_p, world,
+                                      mine, device)
     if gather and world > 1 and out_shared and out is not None:
         # every rank downloads its rows into the shared host array; the barrier orders the
         # writes before rank 0 hands the array back

@@ -344,6 +344,44 @@ int fc_consensus_partition(fc_ctx* ctx, int graph, const void* dev_support, int 
  * every phase without timing reads 0. */
 int fc_consensus_timing(fc_ctx* ctx, double* ms);
 
+/* ---- the consensus hierarchy: every agreement level from one union-find --------------- */
+/* Level s (s = 0..n_total) is the connected components of the edges of H with support(e) >= s:
+ * level 0 is the components of H, and a lower level is coarser.  With root_s(t) the smallest node
+ * of t's component at level s, the levels are the tree
+ *   birth[t] = the largest s with root_s(t) != t, or -1 when t is the smallest node of its
+ *              component of H;   up[t] = root_{birth[t]}(t), or t when birth[t] == -1
+ * (birth[up[t]] < birth[t]): root_s(t) is the end of the walk t -> up[t] -> ... while birth >= s,
+ * and the labels of level s number the roots in node order, as fc_consensus_partition does at an
+ * agreement whose keep rule is support >= s (agreement = (s - 0.5) / n_total, or 0 for s = 0).
+ * Read-only like fc_consensus_partition; all work on the context's stream. */
+typedef struct fc_level_score {
+    int64_t bucket_edges; /* edges with support == s */
+    int64_t k;            /* communities of level s */
+    int64_t max_size;     /* size of the largest */
+    int64_t singletons;
+    int64_t in_weight;    /* sum of w_uv over the edges of H inside a community of level s */
+    uint64_t tot_sq_lo;   /* sum_c (sum_{v in c} weighted degree_v)^2, exact, 128 bits */
+    uint64_t tot_sq_hi;
+    double modularity;    /* fc_part_score's formula from these integers */
+} fc_level_score;
+/* dev_support / n_total / graph exactly as fc_consensus_partition.  birth, up: int32[n] (host, or
+ * device buffers of the context's GPU), levels: fc_level_score[n_total + 1] (host); any may be
+ * NULL.  A level without an edge of its support repeats the record of the level above it, with
+ * bucket_edges = 0.  *best_level: the level that maximises the exact integer
+ * 2 in_weight W2 - tot_sq (modularity's numerator; W2 = total weighted degree), the highest such
+ * level among equals.  Error codes as fc_consensus_partition; nothing is written on error.  The
+ * tree stays in the context for fc_consensus_cut until the next fc_load_graph. */
+int fc_consensus_levels(fc_ctx* ctx, int graph, const void* dev_support, int n_total, int32_t* birth, int32_t* up,
+                        fc_level_score* levels, int32_t* best_level);
+/* labels of level `level` of the last successful fc_consensus_levels (FC_ESTATE if there is none,
+ * FC_EINVAL outside [0, n_total]): labels_out int32[n] in node order, host or device; *k_out
+ * communities. */
+int fc_consensus_cut(fc_ctx* ctx, int level, int32_t* labels_out, int64_t* k_out);
+/* Device time (ms, HIP events) of the phases of the last fc_consensus_levels made with timing
+ * enabled: ms[4] = bucket (histogram, offsets, scatter), tree (init, and a hook and a flatten per
+ * nonempty level), statistics (fold of the per-level counters), join levels. */
+int fc_consensus_levels_timing(fc_ctx* ctx, double* ms);
+
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
  * Writes at most m_cap edges into u/v and the planted community of every node. */
