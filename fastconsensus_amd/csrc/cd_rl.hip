@@ -403,8 +403,17 @@ __device__ __forceinline__ Hdr rl_header(const RL& a, const Unit& u, const Rec& 
 // Ascending sort of K keys held in registers: Batcher's odd-even merge sort (K = 2^k; 63 / 191 /
 // 543 compare-exchanges at K = 16 / 32 / 64 against a bitonic network's 80 / 240 / 672; every
 // index is a compile-time constant, 2 VALU per compare-exchange).
-template <int K>
+// Scheduling fences in the sort and the run passes (every FC_RL_OEM_FENCE compare-exchanges / 8
+// keys; 0: none).  A compare-exchange needs one register beyond its two keys while its min and max
+// stay together, and the passes are serial chains; the scheduler pulls both apart for parallelism
+// a dependent VALU chain does not need here.  Measured on the 64-key W8 kernel bound to 3 waves:
+// 166 VGPRs and no scratch with the fences, 2 VGPRs spilled without them.
+#ifndef FC_RL_OEM_FENCE
+#define FC_RL_OEM_FENCE 8
+#endif
+template <int K, bool FENCED>
 __device__ __forceinline__ void oem_sort(int32_t (&x)[K]) {
+    int n = 0;
 #pragma unroll
     for (int p = 1; p < K; p <<= 1)
 #pragma unroll
@@ -417,6 +426,8 @@ __device__ __forceinline__ void oem_sort(int32_t (&x)[K]) {
                         const int32_t a = x[i + j], b = x[i + j + k];
                         x[i + j] = min(a, b);
                         x[i + j + k] = max(a, b);
+                        if (FENCED && FC_RL_OEM_FENCE && ++n % (FC_RL_OEM_FENCE ? FC_RL_OEM_FENCE : 1) == 0)
+                            __builtin_amdgcn_sched_barrier(0);
                     }
 }
 
@@ -435,7 +446,9 @@ constexpr int WM_WIDE = 0, WM_UNIT = 1, WM_W8 = 2;
 #ifndef FC_RL_SB
 #define FC_RL_SB 16
 #endif
-constexpr int SB = FC_RL_SB;            // Sigma gathers per batch in rl_runs
+#ifndef FC_RL_SB64
+#define FC_RL_SB64 FC_RL_SB             // the 64-key network's own batch
+#endif
 // FC_RL_LPA_OWN (A/B switch, default on): LPA keeps its own-label entries out of the keys too
 // (counted in k_own; the own label a candidate when k_own is the largest count), so a wave whose
 // lanes are all settled (2 k_own > d: own is the unique majority) skips like Louvain's, and the
@@ -445,7 +458,10 @@ constexpr int SB = FC_RL_SB;            // Sigma gathers per batch in rl_runs
 #endif
 // The decision from a lane's K keys ((label << wbits) | weight, -1 for empty and own-label
 // entries -- LPA's too under FC_RL_LPA_OWN): sort, runs, candidates (rl_sorted's second half).
-template <bool LOUV, int K, int WM>
+// TIGHT (the one-unit-per-wave kernels): the fences and opaque values below that keep the scalar
+// and vector register budget down.  The per-lane kernels (n_p = 8: +2.5 % with them) leave the
+// compiler its own schedule.
+template <bool LOUV, int K, int WM, bool TIGHT>
 __device__ __forceinline__ int32_t rl_runs(const RL& a, const Hdr& h, int sweep, int32_t (&x)[K], int32_t own,
                                            long long kown, int32_t tot_own, uint32_t home, unsigned long long& c_dq,
                                            uint32_t& c_unst, uint32_t& c_cand, bool& slow_out) {
@@ -454,7 +470,8 @@ __device__ __forceinline__ int32_t rl_runs(const RL& a, const Hdr& h, int sweep,
     const int wb = UNITW ? 0 : a.wbits;
     const int32_t wm = (1 << wb) - 1;
     const bool wk = h.work;
-    oem_sort<K>(x);
+    oem_sort<K, TIGHT>(x);
+    if (TIGHT && FC_RL_OEM_FENCE) __builtin_amdgcn_sched_barrier(0);
     // run ends and summed weights: e = bit q set when the run of equal labels ends at q
     // pass A: the largest weight vm
     int vm = INT_MIN;
@@ -469,6 +486,7 @@ __device__ __forceinline__ int32_t rl_runs(const RL& a, const Hdr& h, int sweep,
             const bool end = x[q] >= 0 && (q == K - 1 || (x[q + 1] >> wb) != l);
             vm = end ? max(vm, acc) : vm;
             if (!LOUV && !FC_RL_LPA_OWN) kl = (end && l == own) ? acc : kl;
+            if (TIGHT && FC_RL_OEM_FENCE && (q & 7) == 7) __builtin_amdgcn_sched_barrier(0);
         }
         if (!LOUV && !FC_RL_LPA_OWN) kown = kl;
         if (!LOUV && FC_RL_LPA_OWN) vm = max(vm, (int)kown);  // the own label's count is a run too
@@ -481,6 +499,12 @@ __device__ __forceinline__ int32_t rl_runs(const RL& a, const Hdr& h, int sweep,
     // pass B: candidate runs (the runs of weight vm), as bits of cm
     uint32_t cm_lo = 0, cm_hi = 0;
     if (hope) {
+        // Pass B works from the keys alone.  Without this the compiler carries pass A's run sums
+        // (K VGPRs) and its 2K lane masks (scalar pairs, spilled to VGPR lanes) over to here
+        // instead of redoing two compares per key.
+#pragma unroll
+        for (int q = 0; q < K; ++q)
+            if (TIGHT) asm volatile("" : "+v"(x[q]));
         int acc = 0;
 #pragma unroll
         for (int q = 0; q < K; ++q) {
@@ -488,8 +512,14 @@ __device__ __forceinline__ int32_t rl_runs(const RL& a, const Hdr& h, int sweep,
             const int w = UNITW ? 1 : (x[q] & wm);
             acc = (q > 0 && l == (x[q - 1] >> wb)) ? acc + w : w;
             const bool cand = x[q] >= 0 && (q == K - 1 || (x[q + 1] >> wb) != l) && acc == vm;
-            if (q < 32) cm_lo |= (uint32_t)cand << (q & 31);
-            else cm_hi |= (uint32_t)cand << (q & 31);
+            // the bit as a value shifted into place (v_lshl_or): a select between 0 and 1 << q
+            // would take a register per power of two past the inline constants, hoisted out of the
+            // item loop and live through all of it
+            uint32_t cb = cand ? 1u : 0u;
+            if (TIGHT) asm volatile("" : "+v"(cb));
+            if (q < 32) cm_lo |= cb << (q & 31);
+            else cm_hi |= cb << (q & 31);
+            if (TIGHT && FC_RL_OEM_FENCE && (q & 7) == 7) __builtin_amdgcn_sched_barrier(0);
         }
     }
     // LPA, own entries out of the keys: the own label is a candidate when its count is the largest
@@ -505,6 +535,7 @@ __device__ __forceinline__ int32_t rl_runs(const RL& a, const Hdr& h, int sweep,
         // unsigned 64-bit minimum of (Sigma << 32) | ~hash; the hash is a bijection of the id
         // (no id tie is left), inverted for the winner
         uint64_t bkey = ~0ull;
+        constexpr int SB = K == 64 ? FC_RL_SB64 : FC_RL_SB;   // Sigma gathers per batch
         // SB positions per batch: FC_RL_SB (default 16; 8 holds 8 fewer VGPRs live)
 #pragma unroll
         for (int c0 = 0; c0 < K; c0 += SB) {
@@ -568,6 +599,14 @@ __device__ __forceinline__ int32_t rl_runs(const RL& a, const Hdr& h, int sweep,
         }
     }
     return dcs;
+}
+
+// A key handed to a narrower network: the same value, but one the compiler cannot match with the
+// wide network's.  Otherwise it merges the layers the two networks share, runs them ahead of the
+// row-length test, and keeps the wide network's keys alive through the narrow path.
+__device__ __forceinline__ int32_t rl_own_key(int32_t k) {
+    asm volatile("" : "+v"(k));
+    return k;
 }
 
 template <bool LOUV, int K, int WM>
@@ -681,10 +720,10 @@ __device__ __forceinline__ int32_t rl_sorted(const RL& a, const Hdr& h, int swee
             int32_t y[KN];
 #pragma unroll
             for (int j = 0; j < KN; ++j) y[j] = x[j];
-            return rl_runs<LOUV, KN, WM>(a, h, sweep, y, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
+            return rl_runs<LOUV, KN, WM, false>(a, h, sweep, y, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
         }
     }
-    return rl_runs<LOUV, K, WM>(a, h, sweep, x, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
+    return rl_runs<LOUV, K, WM, false>(a, h, sweep, x, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
 }
 
 // ---- one unit per wave (LG = 64: every lane deciding the same vertex, VPW = 1; C4 / C5) ----
@@ -693,6 +732,10 @@ __device__ __forceinline__ int32_t rl_sorted(const RL& a, const Hdr& h, int swee
 // flight while this item sorts), and the label gathers take each neighbour id with a
 // readlane -- a scalar row base (saddr) plus the lane's replica offset, no per-entry address
 // arithmetic and the neighbour-id stage off the item's dependent chain.  Same decisions.
+#ifndef FC_RL_BC
+#define FC_RL_BC 16
+#endif
+constexpr int RL_BC = FC_RL_BC;         // row-id broadcasts (scalar row bases) live at once in rl_sorted_u1
 struct RowPre {
     int32_t col;                 // lane j: entry j's neighbour id (colw: id << wbits | weight)
     int32_t w;                   // WM_WIDE: entry j's weight
@@ -739,12 +782,20 @@ __device__ __forceinline__ int32_t rl_sorted_u1(const RL& a, const Hdr& h, int s
     const uint32_t home = (uint32_t)h.v * ldT + rr;
     const int32_t own = wk ? pre.own : -1;
     int32_t x[K];
+    // RL_BC entries at a time: every gather's row base is a scalar, and K of them hoisted ahead of
+    // the K loads do not fit the scalar file (they were spilled to VGPR lanes and fetched back, a
+    // lane move and its hazard wait each).  Nothing is scheduled across a chunk's end; the gathers
+    // of all chunks still issue back to back, none waits for another.
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
-        // entries past the row repeat entry 0 (same line, a hit) and are masked below
-        const int32_t cj = __builtin_amdgcn_readlane(pre.col, j);
-        const uint32_t id = (uint32_t)(WM == WM_W8 ? (cj >> wb) : cj);
-        x[j] = ld_off(a.lab, id * ldT + rr);                    // id * ldT scalar: one VALU add per entry
+    for (int j0 = 0; j0 < K; j0 += RL_BC) {
+#pragma unroll
+        for (int j = j0; j < j0 + RL_BC && j < K; ++j) {
+            // entries past the row repeat entry 0 (same line, a hit) and are masked below
+            const int32_t cj = __builtin_amdgcn_readlane(pre.col, j);
+            const uint32_t id = (uint32_t)(WM == WM_W8 ? (cj >> wb) : cj);
+            x[j] = ld_off(a.lab, id * ldT + rr);                // id * ldT scalar: one VALU add per entry
+        }
+        __builtin_amdgcn_sched_barrier(0);
     }
     int32_t tot_own = 0;
     if (LOUV) {
@@ -762,6 +813,10 @@ __device__ __forceinline__ int32_t rl_sorted_u1(const RL& a, const Hdr& h, int s
         const bool mine = (LOUV || FC_RL_LPA_OWN) && live && x[j] == own;
         ko += mine ? wj : 0;
         x[j] = (mine || !live) ? -1 : (UNITW ? x[j] : ((x[j] << wb) | wj));
+        // The key is made here, not after the settled test below: left to itself the compiler sinks
+        // the K selects past that test and keeps their 2K lane masks (64-bit scalar pairs) alive
+        // across it -- more than the scalar file, and the bulk of the kernel's scalar spills.
+        asm volatile("" : "+v"(x[j]));
     }
     kown = ko;
     if (LOUV) {
@@ -786,8 +841,8 @@ __device__ __forceinline__ int32_t rl_sorted_u1(const RL& a, const Hdr& h, int s
         if (__builtin_amdgcn_readfirstlane(ds) <= KS1) {
             int32_t y[KS1];
 #pragma unroll
-            for (int j = 0; j < KS1; ++j) y[j] = x[j];
-            return rl_runs<LOUV, KS1, WM>(a, h, sweep, y, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
+            for (int j = 0; j < KS1; ++j) y[j] = rl_own_key(x[j]);
+            return rl_runs<LOUV, KS1, WM, true>(a, h, sweep, y, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
         }
     }
     constexpr int KS = (K == 32 && (FC_RL_SPLIT & 1)) ? 24 : (K == 64 && (FC_RL_SPLIT & 2)) ? 48 : K;
@@ -795,11 +850,11 @@ __device__ __forceinline__ int32_t rl_sorted_u1(const RL& a, const Hdr& h, int s
         if (__builtin_amdgcn_readfirstlane(ds) <= KS) {
             int32_t y[KS];
 #pragma unroll
-            for (int j = 0; j < KS; ++j) y[j] = x[j];
-            return rl_runs<LOUV, KS, WM>(a, h, sweep, y, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
+            for (int j = 0; j < KS; ++j) y[j] = rl_own_key(x[j]);
+            return rl_runs<LOUV, KS, WM, true>(a, h, sweep, y, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
         }
     }
-    return rl_runs<LOUV, K, WM>(a, h, sweep, x, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
+    return rl_runs<LOUV, K, WM, true>(a, h, sweep, x, own, kown, tot_own, home, c_dq, c_unst, c_cand, slow_out);
 }
 
 // Light rows with sortable keys (label and weight fit 31 bits): no LDS, one sorting network
@@ -813,6 +868,18 @@ __device__ __forceinline__ void rl_push_slow(const RL& a, bool slow, int64_t e, 
     if (lane == 0) base = atomicAdd(a.slow_cnt, __popcll(m));
     base = __shfl(base, 0);
     if (slow) a.slow[base + __popcll(m & ((1ull << lane) - 1))] = (e << 14) | (int64_t)rr;
+}
+
+// k_rl_decide's RL argument, read again from the kernel-argument segment (RL is the first
+// argument: offset 0).  The item loop keeps the fields it reads for every item in scalar
+// registers; what only the cold paths read (the counter flush, the slow-visit list, LPA's tie
+// flags) is loaded through this where it is used, a scalar load each, instead of staying live
+// across the loop -- those values were the first the compiler parked in VGPR lanes.  The empty
+// asm hides where the pointer comes from, so the loads are not hoisted back to the entry.
+__device__ __forceinline__ const RL& rl_cold() {
+    auto p = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const RL*)p;
 }
 
 // Occupancy bounds per key width (waves per SIMD; 1 = the compiler's choice): A/B switches
@@ -829,14 +896,24 @@ template <bool LOUV, int K, int WM, bool U1>
 #ifndef FC_RLW24U
 #define FC_RLW24U 4
 #endif
+// 64 keys, one unit per wave (A/B switches; 1 = the compiler's choice, 2 waves).  Bound to 3 waves
+// the W8 kernel fits 166 VGPRs without scratch, but its launches got slower on LFR-1M (19.7 ->
+// 21.7 ms over 5 steps; 19.7 at 2 waves and 193 VGPRs before); the unit-weight kernels (Louvain,
+// LPA) spill 27..40 VGPRs to scratch on the 49..64-entry path at that bound.  Both stay at 1
+// (profiles/r07_rl_decide_resources.txt).
+#ifndef FC_RLW64U
+#define FC_RLW64U 1
+#endif
+#ifndef FC_RLW64U_UNIT
+#define FC_RLW64U_UNIT 1
+#endif
 __global__ __launch_bounds__(RTB)
 __attribute__((amdgpu_waves_per_eu(K <= 16 ? FC_RLW16 : K <= 24 ? (U1 ? FC_RLW24U : FC_RLW32) :
-                                   K <= 32 ? (U1 ? FC_RLW32U : FC_RLW32) : 1)))
+                                   K <= 32 ? (U1 ? FC_RLW32U : FC_RLW32) : (K == 64 && U1) ? (WM == WM_W8 ? FC_RLW64U : FC_RLW64U_UNIT) : 1)))
 void k_rl_decide(RL a, int seg, int ns, int sweep) {
     const int lane = threadIdx.x & 63;
     const int64_t e0 = a.boff[seg], e1 = a.boff[seg + ns];   // degree classes seg .. seg + ns - 1
-    const int64_t items = rl_items(a, e1 - e0);
-    const int LG = a.LG;
+    const int LG = U1 ? 64 : a.LG;
     unsigned long long c_dq = 0;                                // 32-bit counts: one block's items
     uint32_t c_unst = 0, c_vis = 0, c_ent = 0, c_cand = 0, c_units = 0;
     int last_r = -1;
@@ -846,58 +923,94 @@ void k_rl_decide(RL a, int seg, int ns, int sweep) {
             c_dq += __shfl_xor(c_dq, off); c_unst += __shfl_xor(c_unst, off); c_vis += __shfl_xor(c_vis, off);
             c_ent += __shfl_xor(c_ent, off); c_cand += __shfl_xor(c_cand, off); c_units += __shfl_xor(c_units, off);
         }
-        if (lane < LG && r < a.n_r) {
-            if (c_dq) atomicAdd(rl_red(a, r, 0), c_dq);
-            if (c_unst) atomicAdd(rl_red(a, r, 1), (unsigned long long)c_unst);
-            if (c_vis) atomicAdd(rl_red(a, r, 3), (unsigned long long)c_vis);
-            if (c_ent) atomicAdd(rl_red(a, r, 4), (unsigned long long)c_ent);
-            if (c_cand) atomicAdd(rl_red(a, r, 5), (unsigned long long)c_cand);
-            if (c_units) atomicAdd(rl_red(a, r, 6), (unsigned long long)c_units);
+        const RL& cold = U1 ? rl_cold() : a;
+        if (lane < LG && r < cold.n_r) {
+            if (c_dq) atomicAdd(rl_red(cold, r, 0), c_dq);
+            if (c_unst) atomicAdd(rl_red(cold, r, 1), (unsigned long long)c_unst);
+            if (c_vis) atomicAdd(rl_red(cold, r, 3), (unsigned long long)c_vis);
+            if (c_ent) atomicAdd(rl_red(cold, r, 4), (unsigned long long)c_ent);
+            if (c_cand) atomicAdd(rl_red(cold, r, 5), (unsigned long long)c_cand);
+            if (c_units) atomicAdd(rl_red(cold, r, 6), (unsigned long long)c_units);
         }
         c_dq = 0;
         c_unst = c_vis = c_ent = c_cand = c_units = 0;
     };
-    // records two items ahead; U1: the next item's row and own labels one item ahead
-    Rec nxt = U1 ? rl_fetch_u(a, rl_unit(a, e0, e1, blockIdx.x)) : rl_fetch(a, rl_unit(a, e0, e1, blockIdx.x));
-    Rec nx2 = nxt;
-    RowPre pre;
-    pre.col = pre.w = pre.own = 0;
-    if constexpr (U1) {
-        pre = rl_row_pre<WM>(a, rl_unit(a, e0, e1, blockIdx.x), nxt);
-        nx2 = rl_fetch_u(a, rl_unit(a, e0, e1, (int64_t)blockIdx.x + gridDim.x));
-    }
-    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
-        const Unit u = rl_unit(a, e0, e1, w);
-        if (a.banks > 1 && u.r != last_r) flush(last_r);
-        last_r = a.banks > 1 ? u.r : (lane & (LG - 1));
-        const Rec cur = nxt;
-        RowPre pc = pre;
-        if constexpr (U1) {
-            nxt = nx2;
-            pre = rl_row_pre<WM>(a, rl_unit(a, e0, e1, w + gridDim.x), nxt);   // in flight while this item runs
-            nx2 = rl_fetch_u(a, rl_unit(a, e0, e1, w + 2 * (int64_t)gridDim.x));
-        } else {
-            nxt = rl_fetch(a, rl_unit(a, e0, e1, w + gridDim.x));   // in flight while this item runs
-        }
-        const Hdr h = rl_header(a, u, cur);
-        bool slow;
-        const uint32_t cc0 = c_cand;
-        const int32_t dcs = U1 ? rl_sorted_u1<LOUV, K, WM>(a, h, sweep, pc, c_dq, c_unst, c_cand, slow)
-                               : rl_sorted<LOUV, K, WM>(a, h, sweep, c_dq, c_unst, c_cand, slow);
-        rl_push_slow(a, slow, u.e, h.rr);
+    // what follows an item's decision: slow visits, LPA tie flags, counters, the decision row
+    auto finish = [&](const Unit& u, const Hdr& h, int32_t dcs, bool slow, uint32_t cc0) {
+        if (!U1) rl_push_slow(a, slow, u.e, h.rr);
+        else if (__ballot(slow)) rl_push_slow(rl_cold(), slow, u.e, h.rr);   // wave-uniform
         // LPA: the visit's candidates are the labels at the top count (rl_runs adds them to
         // c_cand; a settled lane adds 1), so >= 2 of them is a tie.  Read off the counter rather
         // than returned: one more live value through rl_runs changed the K = 64 kernel's code
         // (205 VGPRs, ~180 SGPR spills) into one that departed from the twin in sweep 0.
         const bool tied = !LOUV && c_cand - cc0 >= 2u;
-        if (!LOUV && FC_LPA_TIES) {                             // LPA ties of tracked replicas: one OR per sub-group
-            const uint64_t tb = __ballot(tied && a.track[h.rr]);
+        if (!LOUV && FC_LPA_TIES && (!U1 || __ballot(tied))) {  // LPA ties of tracked replicas: one OR per sub-group
+            const RL& cold = U1 ? rl_cold() : a;
+            const uint64_t tb = __ballot(tied && cold.track[h.rr]);
             const uint64_t ts = (tb >> (u.s * LG)) & (LG == 64 ? ~0ull : ((1ull << LG) - 1ull));
-            if (u.valid && u.rl == 0 && ts) atomicOr((unsigned long long*)&a.aff[(int64_t)u.bank * a.N + h.v], (unsigned long long)ts);
+            if (u.valid && u.rl == 0 && ts) atomicOr((unsigned long long*)&cold.aff[(int64_t)u.bank * cold.N + h.v], (unsigned long long)ts);
         }
         if (h.work) { c_vis += 1; c_ent += (uint32_t)h.d; }
         if (u.valid && u.rl == 0 && h.msk) c_units += 1;
         if (u.valid && h.rr < a.n_r) a.dec[u.e * a.ldT + h.rr] = h.work ? dcs : -1;
+    };
+    if constexpr (U1) {
+        // One unit per wave: item w is entry e0 + w / banks of bank w % banks, the same for every
+        // lane.  The loop steps (entry, bank) by gridDim.x items in scalars -- one division per
+        // kernel instead of rl_unit's 64-bit one for each of the three items in flight -- and
+        // holds the records two items ahead, the next item's row and own labels one item ahead.
+        const int banks = a.banks;
+        const uint32_t ge = gridDim.x / (uint32_t)banks, gb = gridDim.x % (uint32_t)banks;
+        auto unit_of = [&](int64_t e, int bank) {
+            Unit u;
+            u.e = e; u.bank = bank; u.s = 0; u.rl = lane; u.r = bank * 64 + lane;
+            u.valid = e < e1;
+            return u;
+        };
+        auto step = [&](int64_t& e, int& bank) {
+            e += ge; bank += (int)gb;
+            if (bank >= banks) { bank -= banks; ++e; }
+        };
+        int64_t en = e0 + blockIdx.x / (uint32_t)banks;
+        int bn = (int)(blockIdx.x % (uint32_t)banks);
+        Rec nxt = rl_fetch_u(a, unit_of(en, bn));
+        RowPre pre = rl_row_pre<WM>(a, unit_of(en, bn), nxt);
+        int64_t e2 = en;
+        int b2 = bn;
+        step(e2, b2);
+        Rec nx2 = rl_fetch_u(a, unit_of(e2, b2));
+        while (en < e1) {
+            const Unit u = unit_of(en, bn);
+            if (banks > 1 && u.r != last_r) flush(last_r);
+            last_r = banks > 1 ? u.r : lane;
+            const Rec cur = nxt;
+            const RowPre pc = pre;
+            en = e2; bn = b2;
+            nxt = nx2;
+            pre = rl_row_pre<WM>(a, unit_of(en, bn), nxt);      // in flight while this item runs
+            step(e2, b2);
+            nx2 = rl_fetch_u(a, unit_of(e2, b2));
+            const Hdr h = rl_header(a, u, cur);
+            bool slow;
+            const uint32_t cc0 = c_cand;
+            const int32_t dcs = rl_sorted_u1<LOUV, K, WM>(a, h, sweep, pc, c_dq, c_unst, c_cand, slow);
+            finish(u, h, dcs, slow, cc0);
+        }
+    } else {
+        const int64_t items = rl_items(a, e1 - e0);
+        Rec nxt = rl_fetch(a, rl_unit(a, e0, e1, blockIdx.x));  // the record one item ahead
+        for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
+            const Unit u = rl_unit(a, e0, e1, w);
+            if (a.banks > 1 && u.r != last_r) flush(last_r);
+            last_r = a.banks > 1 ? u.r : (lane & (LG - 1));
+            const Rec cur = nxt;
+            nxt = rl_fetch(a, rl_unit(a, e0, e1, w + gridDim.x));   // in flight while this item runs
+            const Hdr h = rl_header(a, u, cur);
+            bool slow;
+            const uint32_t cc0 = c_cand;
+            const int32_t dcs = rl_sorted<LOUV, K, WM>(a, h, sweep, c_dq, c_unst, c_cand, slow);
+            finish(u, h, dcs, slow, cc0);
+        }
     }
     flush(last_r);
 }

@@ -230,8 +230,9 @@ struct Ctx {
     int timer_chain = getenv("FC_TIMER_CHAIN") ? atoi(getenv("FC_TIMER_CHAIN")) : 1;
     // replica-lane decide launches per bucket: 3 (networks of 16 / 32 / 64 keys), 4 (+48) or 5
     // (+24 and 48) -- per algorithm (cd_rl.hip, degree classes); 2: one launch for the rows of
-    // <= 32 and one for 33..64, the one-unit-per-wave kernels picking the network per row
-    // (FC_RL_SPLIT; other layouts run 3)
+    // <= 32 and one for 33..64, each kernel picking the narrower network in the launch: the
+    // one-unit-per-wave kernels per row, the per-lane ones by the wave's longest row (FC_RL_SPLIT
+    // bits 8 and 16, both set by default; a build without them runs 3 for the per-lane layouts)
     int rl_groups_louv = getenv("FC_RL_GROUPS_LOUV") ? atoi(getenv("FC_RL_GROUPS_LOUV")) : 2;
     int rl_groups_lpa = getenv("FC_RL_GROUPS_LPA") ? atoi(getenv("FC_RL_GROUPS_LPA")) : 2;
     // partition scoring (score.h): the reference labeling in slot order, one row's sort / segment
