@@ -59,9 +59,6 @@ static constexpr int HCAP = 64;         // slots per tile table (>= LIGHT_MAX_DE
 static constexpr int LIGHT_MAX_DEG = 64;
 static constexpr int HEAVY_LDS_SLOTS = 4096;
 static constexpr int HEAVY_GRID = 256;
-static constexpr double DQ_SCALE = 1099511627776.0;  // 2^40 fixed point for predicted dQ
-static constexpr int NSH = 16;          // counter shards per replica
-static constexpr int RF = 8;            // fields: 0 dq, 1 unstable, 2 moves, 3 verts, 4 entries, 5 cands
 static constexpr int RR_FULL = 1, RR_PUSH = 2, RR_TRANS = 4;   // round-record flags
 
 
@@ -147,7 +144,7 @@ struct CDArgs {
 // with a fixed grid, two vertices closer than CHUNK would share a chunk -- and so decide
 // simultaneously -- in every sweep (a dyad whose ends each join the other's singleton then
 // swaps forever; LFR-1M final pass: 200 sweeps).  The chunk domain has room for the shift
-// (cd_run: NC = (N + 2*CHUNK - 2) / CHUNK).  oracle/fc_oracle.c tw_pos_vertex restates it.
+// (SweepGeom: NC = (N + 2*CHUNK - 2) / CHUNK).  oracle/fc_oracle.c tw_pos_vertex restates it.
 __device__ __forceinline__ Perm sweep_perm(const CDArgs& a, int rg, int sweep) {
     Perm P = make_perm(a.perm_n, stream_key(a.seed, (uint32_t)rg, a.iter, (uint32_t)sweep, 1));
     if (a.chunk) P.off = stream_key(a.seed, (uint32_t)rg, a.iter, (uint32_t)sweep, 3) & (CHUNK - 1);
@@ -1369,26 +1366,6 @@ __global__ __launch_bounds__(256) void k_list_fill(CDArgs a, int sweep, const in
         lr[s_base[k] + atomicAdd(&s_cnt[k], 1)] = (int32_t)v;
     }
 }
-// One bucket: decide (light + heavy rows) against the state left by earlier buckets, apply.
-// Every grid is fixed and every size is read on the device, so a sweep never waits on
-// the host.
-template <bool LOUV, typename TT>
-static void sub_round(Ctx& c, const CDArgs& a, int k, int sweep, bool any_heavy, int X) {
-    (void)any_heavy;   // heavy_cnt: zeroed at cd_run start, then by each round's k_apply
-    const int ev = timer_begin(c);
-    // one item per block: X item slots per replica, rounded up to whole XCD groups of 8
-    const int64_t grid = (((int64_t)a.n_r * X + 7) / 8) * 8;
-    k_decide_light<LOUV, TT><<<(unsigned)grid, DTB, 0, c.stream>>>(a, k, sweep, X);
-    timer_end(c, 4, ev);
-    if (any_heavy) k_decide_heavy<LOUV, TT><<<HEAVY_GRID, TB, 0, c.stream>>>(a, k, sweep);
-    // apply: FC_APPLY_BLOCKS blocks per replica, more when few replicas share the GPU (a
-    // push/tracking move is a dependent row walk, so the chip needs ~2K resident blocks), but
-    // no more than the round's decisions fill (16-lane tiles)
-    const int64_t ab = std::min<int64_t>(std::max<int64_t>(c.apply_blocks, (2048 + a.n_r - 1) / a.n_r),
-                                         std::max<int64_t>(1, ((int64_t)X * LNT + TILES - 1) / TILES));
-    k_apply<LOUV, TT><<<dim3((unsigned)ab, a.n_r), ATB, 0, c.stream>>>(a, k);
-}
-
 __global__ void k_count_heavy(int64_t n, const int64_t* rowptr, int64_t thr, unsigned long long* out) {
     const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool h = v < n && rowptr[v + 1] - rowptr[v] > thr;
@@ -1405,185 +1382,239 @@ static int64_t count_heavy(Ctx& c, int64_t thr) {
     return c.hpin[0];
 }
 
-void cd_run(Ctx& c, int algo, int rbegin, int rcount, int n_p_total, int iteration, int shared_full,
-            const CDHandoff* h) {
-    FC_REQUIRE(rcount >= 1 && rbegin >= 0 && rbegin + rcount <= n_p_total, FC_EINVAL, "bad replica range");
-    FC_REQUIRE(c.N > 0 && c.g.rowptr.p, FC_ESTATE, "no graph loaded");
-    const int sl0 = timer_begin(c);
-    const bool louv = is_louvain(algo);
-    const int64_t N = c.N;
-    Graph& g = c.g;
-    c.n_r = rcount; c.rbase = rbegin; c.n_p_total = n_p_total;
-    c.labT_valid = false;
-    // sweep positions: vertices in a random order, or whole chunks of CHUNK consecutive
-    // vertices in a random chunk order (coalesced per-vertex accesses)
-    const int CH = c.chunk;
-    const int64_t NC = CH ? (N + 2 * CH - 2) / CH : N;   // room for the chunk-grid shift (sweep_perm)
-    const int B = (int)std::min<int64_t>(cd_buckets(c, algo), NC);
-    const int64_t S = CH ? ((NC + B - 1) / B) * CH : (N + B - 1) / B;
-    int32_t* lab = ensure<int32_t>(c.lab, (size_t)rcount * N);
-    // tot in int32 whenever every community total fits (all <= 2M < 2^31): half the gathers
-    const bool tot32 = g.M2 <= 0x7fffffffll && !c.order_pass;
-    void* tot = louv ? (void*)ensure<int64_t>(c.tot, (size_t)rcount * N) : nullptr;
-    const int64_t PN = CH ? NC * CH : N;
-    int4* dec = ensure<int4>(c.dec, (size_t)rcount * PN);   // a coarse round may hold up to PN decisions
-    const int64_t m2 = 2 * g.m;
-    int32_t* nlab = ensure<int32_t>(c.nlab, (size_t)rcount * (m2 > 0 ? m2 : 1));
-    // per-replica state: active i32 [n_r] | red u64 [n_r][NSH][RF] | sacc u64 [n_r][4] | n_active
-    char* rs = (char*)ensure<char>(c.rep_state, (size_t)rcount * (4 + 8 * NSH * RF + 64) + 256);
-    int32_t* active = (int32_t*)rs;
-    unsigned long long* red = (unsigned long long*)(rs + (((size_t)rcount * 4 + 255) & ~size_t(255)));
-    unsigned long long* sacc = red + (size_t)rcount * NSH * RF;
-    int32_t* n_active = (int32_t*)(sacc + 4 * (size_t)rcount);   // see k_sweep_end
-    unsigned long long* tail_acc = (unsigned long long*)(n_active + 8);   // [n_r][4] k_cd_tail visits
-    const size_t zero_bytes = (char*)(tail_acc + 4 * (size_t)rcount) - (char*)red;
-    // heavy rows (degree > LIGHT_MAX_DEG): at most one entry per heavy vertex and replica per round
-    int64_t n_heavy = 0;
-    if (g.max_deg > LIGHT_MAX_DEG) n_heavy = count_heavy(c, LIGHT_MAX_DEG);
-    int32_t* heavy = ensure<int32_t>(c.heavy_list, 3 * (size_t)rcount * (size_t)std::max<int64_t>(n_heavy, 1) + 3);
-    const int64_t aw = (N + 31) / 32;
-    uint32_t* aff = ensure<uint32_t>(c.aff, (size_t)rcount * aw);
-    int32_t* track = ensure<int32_t>(c.track, 4 * (size_t)rcount);
-    if (!h) {
-        FC_HIP(hipMemsetAsync(aff, 0, 4 * (size_t)rcount * aw, c.stream));
-        FC_HIP(hipMemsetAsync(track, 0, 16 * (size_t)rcount, c.stream));   // pull mode, no tracking
-    }
-    int32_t* list = ensure<int32_t>(c.vlist, (size_t)rcount * PN);
-    // rrec int4 [B][n_r] | lcnt [B][n_r] | cntfine [n_r][B] | loff [n_r][B+1] | cursor [n_r][B] | gco [n_r] | info [8]
-    const size_t plan_ints = 4 * (size_t)B * rcount + (size_t)B * rcount + (size_t)rcount * B +
-                             (size_t)rcount * (B + 1) + (size_t)rcount * B + rcount + 1 + 8;
-    int4* rrec = (int4*)ensure<int32_t>(c.vcnt, plan_ints);
-    int32_t* lcnt = (int32_t*)(rrec + (size_t)B * rcount);
-    int32_t* cntfine = lcnt + (size_t)B * rcount;
-    int32_t* loff = cntfine + (size_t)rcount * B;
-    int32_t* cursor = loff + (size_t)rcount * (B + 1);
-    int32_t* gco = cursor + (size_t)rcount * B;
-    // [0] max rounds, [1] decide item slots per replica (its largest round), [2..3] u64 visits
-    // (8-byte aligned: 64-bit atomics), [4] the largest replica's visits
-    int32_t* info = gco + rcount;
-    if ((uintptr_t)info & 7) ++info;
-    int32_t* heavy_cnt = ensure<int32_t>(c.heavy_cnt, 4);
-    FC_HIP(hipMemsetAsync(heavy_cnt, 0, sizeof(int32_t), c.stream));
-    int64_t heavy_slots = 1;
-    while (heavy_slots < 2 * (int64_t)g.max_deg) heavy_slots <<= 1;
-    int32_t* hscr = nullptr;
-    if (heavy_slots > HEAVY_LDS_SLOTS)   // one slice per heavy-kernel block, or per tail-kernel block (replica)
-        hscr = ensure<int32_t>(c.heavy_scratch, (size_t)std::max(HEAVY_GRID, rcount) * 2 * heavy_slots);
+// ------------------------------------------------------------------ driver
+// f(TT) / f(LOUV, TT) with the run-time values as compile-time constants, for the kernels'
+// template arguments: TT the type of the community totals (int32 whenever they fit), which LPA
+// does not keep -- <false, int64_t> is never instantiated
+template <class T> struct TotType { using type = T; };
+template <class F> static void cd_dispatch(bool tot32, F&& f) {
+    if (tot32) f(TotType<int32_t>{});
+    else f(TotType<int64_t>{});
+}
+template <class F> static void cd_dispatch(bool louv, bool tot32, F&& f) {
+    if (!louv) f(std::false_type{}, TotType<int32_t>{});
+    else cd_dispatch(tot32, [&](auto tt) { f(std::true_type{}, tt); });
+}
 
-    if (!h) {
-        std::vector<int32_t> ones(rcount, (g.M2 > 0) ? 1 : 0);
-        FC_HIP(hipMemcpyAsync(active, ones.data(), sizeof(int32_t) * rcount, hipMemcpyHostToDevice, c.stream));
-        sync(c);  // `ones` is pageable host memory
-    }
-    FC_HIP(hipMemsetAsync(red, 0, zero_bytes, c.stream));
-    dim3 ig(nblk(N), rcount);
-    const int32_t* spos = c.spos.as<int32_t>();
-    const int32_t* sinv = c.sinv.as<int32_t>();
-    if (h) {   // a hybrid batch from its first filtered sweep: the replica-lane engine's state
-        FC_REQUIRE(tot32 || !louv, FC_ESTATE, "hybrid hand-off needs int32 totals");
-        h->fill(c, h->user, lab, (int32_t*)tot, aff, track, active, nlab);
-    } else if (tot32) {
-        k_cd_init<int32_t><<<ig, TB, 0, c.stream>>>(N, rcount, g.kdeg.as<int64_t>(), sinv, lab, (int32_t*)tot, louv ? 1 : 0);
-    } else {
-        k_cd_init<int64_t><<<ig, TB, 0, c.stream>>>(N, rcount, g.kdeg.as<int64_t>(), sinv, lab, (int64_t*)tot, louv ? 1 : 0);
-    }
-    FC_REQUIRE(!louv || (double)g.max_kdeg * (double)g.M2 < 4.0e18, FC_ELIMIT,
-               "edge weights too large for exact int64 modularity gains");
-
+// The state of one cd_run() run; its methods are the phases, in the order cd_run() calls them.
+struct CdRun {
+    Ctx& c;
+    Graph& g;
+    const bool louv;
+    const bool tot32;            // int32 totals: every community total fits (all <= 2M < 2^31), half the gathers
+    const bool hv;               // the graph has heavy rows (degree > LIGHT_MAX_DEG)
+    const int iteration, n_r;
+    const int64_t N;
+    const SweepGeom geo;
+    const int sweep0;            // a hand-off's first sweep (else 0)
     CDArgs a;
-    a.N = N; a.S = S; a.PN = PN; a.B = B; a.dstride = PN; a.coarsen = louv ? c.coarsen : 0; a.chunk = CH; a.perm_n = (uint32_t)NC; a.n_r = rcount; a.rbase = rbegin; a.iter = (uint32_t)iteration; a.seed = c.seed;
-    a.rowptr = g.rowptr.as<int64_t>(); a.col = g.col.as<int32_t>(); a.cw = g.cw.as<int32_t>();
-    a.colp = g.colp.as<int32_t>(); a.spos = spos; a.vrec = g.vrec.as<int4>();
-    a.kdeg = g.kdeg.as<int64_t>(); a.M2 = g.M2;
-    a.lab = lab; a.tot = tot; a.dec = dec; a.active = active;
-    a.nlab = nlab; a.rev = g.crev.as<int32_t>(); a.m2 = m2;
-    a.red = red; a.sacc = sacc;
-    a.min_dq = c.cd_min_dq;
-    a.shared_full = shared_full;
-    // hybrid: per-replica list sizes of the filtered sweeps (dense lists keep the shared order)
-    int32_t* vcnt = (shared_full && c.prune && c.dense_div) ? ensure<int32_t>(c.aff_cnt, (size_t)rcount) : nullptr;
-    a.vcnt = vcnt;
-    a.dense_div = c.dense_div;
-    a.heavy = heavy; a.heavy_cnt = heavy_cnt; a.heavy_scratch = hscr; a.heavy_slots = heavy_slots;
-    a.aff = aff; a.aw = aw; a.list = list; a.loff = loff; a.lcnt = lcnt; a.rrec = rrec; a.track = track; a.prune = c.prune;
-    a.hcap = std::max<int64_t>(n_heavy, 1);
-    a.track_div = c.track_div;
-    // push mode only on unit-weight graphs: on consensus graphs the pull sweeps measured
-    // faster (LFR-1M weighted CD batch 46.1 vs 47.1 ms; input graph 125.7 vs 129.6 with push);
-    // the mode never changes a decision
-    a.push_div = (louv && g.max_w > 1) ? 0 : c.push_div;
-    // Leiden-style marking on consensus graphs (weights > 1; LPA ignores them but runs on the
-    // same strongly clustered graph): after the first sweep few vertices move, and nearly all
-    // the later movers have a neighbour that ended in another community (LFR-100k consensus
-    // graph: 1.5 % of the vertices marked after sweep 1, covering 99.6-100 % of sweep 2's
-    // movers, against 85 % marked by "every neighbour of a mover").  Sweep 2 is already
-    // filtered, so no unfiltered sweep is left for the pull -> push transition: lm is pull-only.
-    a.lm = ((g.max_w > 1 || c.prune_mark == 2) && c.prune && c.prune_mark >= 1) ? 1 : 0;
-    if (a.lm) a.push_div = 0;
-    a.mvf = nullptr;
-    if (a.lm) {
-        a.mvf = ensure<uint8_t>(c.mvf, (size_t)rcount * N);
-        FC_HIP(hipMemsetAsync(a.mvf, 0, (size_t)rcount * N, c.stream));
+    // the sweep plan (k_list_count / k_list_plan / k_list_fill) and the per-replica state
+    int32_t *cntfine, *loff, *cursor, *gco, *lcnt, *info, *list, *vcnt, *n_active;
+    int4* rrec;
+    unsigned long long* tail_acc;
+    int32_t* hinfo;              // pinned: info[0..4] | n_active[0] at [6]
+    unsigned lb_grid;            // flag scans: one 32-vertex word per thread
+    dim3 ig;
+    int sweep;
+    // the current sweep, from its one host read
+    int rounds = 0;
+    unsigned long long visits = 0;
+
+    // set-up: the batch's buffers, the launch arguments and the initial state -- singletons, or
+    // (h) what the replica-lane engine hands over
+    CdRun(Ctx& c_, int algo, int rbegin, int rcount, int n_p_total, int iteration_, int shared_full, const CDHandoff* h)
+        : c(c_), g(c_.g), louv(is_louvain(algo)), tot32(c_.g.M2 <= 0x7fffffffll && !c_.order_pass),
+          hv(c_.g.max_deg > LIGHT_MAX_DEG), iteration(iteration_), n_r(rcount), N(c_.N), geo(c_, algo),
+          sweep0(h ? h->sweep0 : 0), sweep(sweep0) {
+        c.n_r = rcount; c.rbase = rbegin; c.n_p_total = n_p_total;
+        c.labT_valid = false;
+        const int B = geo.B;
+        const int64_t PN = geo.PN;
+        int32_t* lab = ensure<int32_t>(c.lab, (size_t)rcount * N);
+        void* tot = louv ? (void*)ensure<int64_t>(c.tot, (size_t)rcount * N) : nullptr;
+        int4* dec = ensure<int4>(c.dec, (size_t)rcount * PN);   // a coarse round may hold up to PN decisions
+        const int64_t m2 = 2 * g.m;
+        int32_t* nlab = ensure<int32_t>(c.nlab, (size_t)rcount * (m2 > 0 ? m2 : 1));
+        // per-replica state: active i32 [n_r] | red u64 [n_r][NSH][RF] | sacc u64 [n_r][4] | n_active | tail_acc
+        char* rs = (char*)ensure<char>(c.rep_state, (size_t)rcount * (4 + 8 * NSH * RF + 64) + 256);
+        int32_t* active = (int32_t*)rs;
+        unsigned long long* red = (unsigned long long*)(rs + (((size_t)rcount * 4 + 255) & ~size_t(255)));
+        unsigned long long* sacc = red + (size_t)rcount * NSH * RF;
+        n_active = (int32_t*)(sacc + 4 * (size_t)rcount);   // see k_sweep_end
+        tail_acc = (unsigned long long*)(n_active + 8);     // [n_r][4] k_cd_tail visits
+        const size_t zero_bytes = (char*)(tail_acc + 4 * (size_t)rcount) - (char*)red;
+        // heavy rows: at most one entry per heavy vertex and replica per round
+        int64_t n_heavy = 0;
+        if (hv) n_heavy = count_heavy(c, LIGHT_MAX_DEG);
+        int32_t* heavy = ensure<int32_t>(c.heavy_list, 3 * (size_t)rcount * (size_t)std::max<int64_t>(n_heavy, 1) + 3);
+        const int64_t aw = (N + 31) / 32;
+        uint32_t* aff = ensure<uint32_t>(c.aff, (size_t)rcount * aw);
+        int32_t* track = ensure<int32_t>(c.track, 4 * (size_t)rcount);
+        if (!h) {
+            FC_HIP(hipMemsetAsync(aff, 0, 4 * (size_t)rcount * aw, c.stream));
+            FC_HIP(hipMemsetAsync(track, 0, 16 * (size_t)rcount, c.stream));   // pull mode, no tracking
+        }
+        list = ensure<int32_t>(c.vlist, (size_t)rcount * PN);
+        // rrec int4 [B][n_r] | lcnt [B][n_r] | cntfine [n_r][B] | loff [n_r][B+1] | cursor [n_r][B] | gco [n_r] | info [8]
+        const size_t plan_ints = 4 * (size_t)B * rcount + (size_t)B * rcount + (size_t)rcount * B +
+                                 (size_t)rcount * (B + 1) + (size_t)rcount * B + rcount + 1 + 8;
+        rrec = (int4*)ensure<int32_t>(c.vcnt, plan_ints);
+        lcnt = (int32_t*)(rrec + (size_t)B * rcount);
+        cntfine = lcnt + (size_t)B * rcount;
+        loff = cntfine + (size_t)rcount * B;
+        cursor = loff + (size_t)rcount * (B + 1);
+        gco = cursor + (size_t)rcount * B;
+        // [0] max rounds, [1] decide item slots per replica (its largest round), [2..3] u64 visits
+        // (8-byte aligned: 64-bit atomics), [4] the largest replica's visits
+        info = gco + rcount;
+        if ((uintptr_t)info & 7) ++info;
+        int32_t* heavy_cnt = ensure<int32_t>(c.heavy_cnt, 4);
+        FC_HIP(hipMemsetAsync(heavy_cnt, 0, sizeof(int32_t), c.stream));   // then zeroed by each round's k_apply
+        int64_t heavy_slots = 1;
+        while (heavy_slots < 2 * (int64_t)g.max_deg) heavy_slots <<= 1;
+        int32_t* hscr = nullptr;
+        if (heavy_slots > HEAVY_LDS_SLOTS)   // one slice per heavy-kernel block, or per tail-kernel block (replica)
+            hscr = ensure<int32_t>(c.heavy_scratch, (size_t)std::max(HEAVY_GRID, rcount) * 2 * heavy_slots);
+
+        if (!h) {
+            std::vector<int32_t> ones(rcount, (g.M2 > 0) ? 1 : 0);
+            FC_HIP(hipMemcpyAsync(active, ones.data(), sizeof(int32_t) * rcount, hipMemcpyHostToDevice, c.stream));
+            sync(c);  // `ones` is pageable host memory
+        }
+        FC_HIP(hipMemsetAsync(red, 0, zero_bytes, c.stream));
+        ig = dim3(nblk(N), rcount);
+        const int32_t* sinv = c.sinv.as<int32_t>();
+        if (h) {   // a hybrid batch from its first filtered sweep: the replica-lane engine's state
+            FC_REQUIRE(tot32 || !louv, FC_ESTATE, "hybrid hand-off needs int32 totals");
+            h->fill(c, h->user, lab, (int32_t*)tot, aff, track, active, nlab);
+        } else {
+            cd_dispatch(tot32, [&](auto tt) {
+                using TT = typename decltype(tt)::type;
+                k_cd_init<TT><<<ig, TB, 0, c.stream>>>(N, rcount, g.kdeg.as<int64_t>(), sinv, lab, (TT*)tot, louv ? 1 : 0);
+            });
+        }
+        FC_REQUIRE(!louv || (double)g.max_kdeg * (double)g.M2 < 4.0e18, FC_ELIMIT,
+                   "edge weights too large for exact int64 modularity gains");
+
+        a.N = N; a.S = geo.S; a.PN = PN; a.B = B; a.dstride = PN; a.coarsen = louv ? c.coarsen : 0; a.chunk = geo.CH;
+        a.perm_n = (uint32_t)geo.NC; a.n_r = rcount; a.rbase = rbegin; a.iter = (uint32_t)iteration; a.seed = c.seed;
+        a.rowptr = g.rowptr.as<int64_t>(); a.col = g.col.as<int32_t>(); a.cw = g.cw.as<int32_t>();
+        a.colp = g.colp.as<int32_t>(); a.spos = c.spos.as<int32_t>(); a.vrec = g.vrec.as<int4>();
+        a.kdeg = g.kdeg.as<int64_t>(); a.M2 = g.M2;
+        a.lab = lab; a.tot = tot; a.dec = dec; a.active = active;
+        a.nlab = nlab; a.rev = g.crev.as<int32_t>(); a.m2 = m2;
+        a.red = red; a.sacc = sacc;
+        a.min_dq = c.cd_min_dq;
+        a.shared_full = shared_full;
+        // hybrid: per-replica list sizes of the filtered sweeps (dense lists keep the shared order)
+        vcnt = (shared_full && c.prune && c.dense_div) ? ensure<int32_t>(c.aff_cnt, (size_t)rcount) : nullptr;
+        a.vcnt = vcnt;
+        a.dense_div = c.dense_div;
+        a.heavy = heavy; a.heavy_cnt = heavy_cnt; a.heavy_scratch = hscr; a.heavy_slots = heavy_slots;
+        a.aff = aff; a.aw = aw; a.list = list; a.loff = loff; a.lcnt = lcnt; a.rrec = rrec; a.track = track; a.prune = c.prune;
+        a.hcap = std::max<int64_t>(n_heavy, 1);
+        a.track_div = c.track_div;
+        // push mode only on unit-weight graphs: on consensus graphs the pull sweeps measured
+        // faster (LFR-1M weighted CD batch 46.1 vs 47.1 ms; input graph 125.7 vs 129.6 with push);
+        // the mode never changes a decision
+        a.push_div = (louv && g.max_w > 1) ? 0 : c.push_div;
+        // Leiden-style marking on consensus graphs (weights > 1; LPA ignores them but runs on the
+        // same strongly clustered graph): after the first sweep few vertices move, and nearly all
+        // the later movers have a neighbour that ended in another community (LFR-100k consensus
+        // graph: 1.5 % of the vertices marked after sweep 1, covering 99.6-100 % of sweep 2's
+        // movers, against 85 % marked by "every neighbour of a mover").  Sweep 2 is already
+        // filtered, so no unfiltered sweep is left for the pull -> push transition: lm is pull-only.
+        a.lm = cd_leiden_marks(c) ? 1 : 0;
+        if (a.lm) a.push_div = 0;
+        a.mvf = nullptr;
+        if (a.lm) {
+            a.mvf = ensure<uint8_t>(c.mvf, (size_t)rcount * N);
+            FC_HIP(hipMemsetAsync(a.mvf, 0, (size_t)rcount * N, c.stream));
+        }
+        a.unitw = cd_unit_weights(c, louv) ? 1 : 0;
+        a.wbits = 1;
+        if (louv) while (a.wbits < 31 && (g.max_w >> a.wbits) != 0) ++a.wbits;
+        // own-label register sums (one ballot per load) for the entries of the graph's typical
+        // weight w0; the rest of a weighted row keeps the table (a full wave scan of weighted own
+        // sums measured slower: LFR-1M consensus graph decide 32.7 vs 29.0 ms per batch)
+        a.own_bal = c.own_ballot ? 1 : 0;
+        a.w0 = a.wbits == 1 ? 1 : std::max(1, n_p_total);
+
+        lb_grid = (unsigned)((aw + TB - 1) / TB);
+        hinfo = (int32_t*)(c.hpin + 8);
+        if (c.trace && !h) { sync(c); trace_dt_us(true); }   // a hand-off's first sweep includes the conversion
+        FC_HIP(hipMemsetAsync(cntfine, 0, sizeof(int32_t) * (size_t)rcount * geo.B, c.stream));   // then kept zero by k_list_plan
     }
-    a.unitw = (!louv || (g.max_w == 1 && g.M2 == 2 * g.m)) ? 1 : 0;
-    a.wbits = 1;
-    if (louv) while (a.wbits < 31 && (g.max_w >> a.wbits) != 0) ++a.wbits;
-    // own-label register sums (one ballot per load) for the entries of the graph's typical
-    // weight w0; the rest of a weighted row keeps the table (a full wave scan of weighted own
-    // sums measured slower: LFR-1M consensus graph decide 32.7 vs 29.0 ms per batch)
-    a.own_bal = c.own_ballot ? 1 : 0;
-    a.w0 = a.wbits == 1 ? 1 : std::max(1, n_p_total);
 
     // One host round trip per sweep, after the visit lists are planned: it returns the number
     // of rounds (coarse buckets) and the largest per-replica round (decide item slots), so
     // every launch is sized exactly, plus the active count left by the previous sweep.
-    const bool hv = g.max_deg > LIGHT_MAX_DEG;
-    const unsigned lb_grid = (unsigned)((aw + TB - 1) / TB);   // flag scans: one 32-vertex word per thread
-    int32_t* hinfo = (int32_t*)(c.hpin + 8);   // info[0..4] | n_active[0] at [6]
-    const int sweep0 = h ? h->sweep0 : 0;
-    int sweep = sweep0;
-    if (c.trace && !h) { sync(c); trace_dt_us(true); }   // a hand-off's first sweep includes the conversion
-    FC_HIP(hipMemsetAsync(cntfine, 0, sizeof(int32_t) * (size_t)rcount * B, c.stream));   // then kept zero by k_list_plan
-    for (; sweep < c.max_sweeps && g.M2 > 0; ++sweep) {
+    // False: every replica has stopped.
+    bool plan_sweep() {
         if (vcnt && sweep > 0) {
-            FC_HIP(hipMemsetAsync(vcnt, 0, sizeof(int32_t) * (size_t)rcount, c.stream));
-            k_aff_count<<<dim3(lb_grid, rcount), TB, 0, c.stream>>>(a, vcnt);
+            FC_HIP(hipMemsetAsync(vcnt, 0, sizeof(int32_t) * (size_t)n_r, c.stream));
+            k_aff_count<<<dim3(lb_grid, n_r), TB, 0, c.stream>>>(a, vcnt);
         }
-        k_list_count<<<dim3(lb_grid, rcount), TB, sizeof(int) * B, c.stream>>>(a, sweep, cntfine);
+        k_list_count<<<dim3(lb_grid, n_r), TB, sizeof(int) * geo.B, c.stream>>>(a, sweep, cntfine);
         k_list_plan<<<1, TB, 0, c.stream>>>(a, cntfine, loff, cursor, gco, lcnt, rrec, info, n_active);
         FC_HIP(hipMemcpyAsync(hinfo, info, 28, hipMemcpyDeviceToHost, c.stream));
         sync(c);
-        const int rounds = hinfo[0];
-        const unsigned long long visits = *(unsigned long long*)(hinfo + 2);
-        if (rounds == 0 || (sweep > sweep0 && hinfo[6] == 0)) break;   // every replica has stopped
-        // small sweeps (every replica visits <= tail_visits vertices): hand every remaining
-        // sweep to the per-replica tail kernel (it takes the flags as its first worklist)
+        rounds = hinfo[0];
+        visits = *(const unsigned long long*)(hinfo + 2);
+        return !(rounds == 0 || (sweep > sweep0 && hinfo[6] == 0));
+    }
+
+    void fill_list() {
+        k_list_fill<<<dim3(lb_grid, n_r), TB, 2 * sizeof(int) * geo.B, c.stream>>>(a, sweep, gco, cursor, list);
+    }
+
+    // small sweeps (every replica visits <= tail_visits vertices): hand every remaining sweep
+    // to the per-replica tail kernel (it takes the flags as its first worklist).  True: done so.
+    bool tail() {
         const int64_t tail_thr = c.tail_visits >= 0 ? c.tail_visits : (louv ? 1024 : 4096);
-        if (tail_thr > 0 && (int64_t)hinfo[4] <= tail_thr && B <= TAIL_MAXB) {
-            int32_t* tbuf = ensure<int32_t>(c.tailbuf, (size_t)rcount * 3 * N);
-            int32_t* tmark = ensure<int32_t>(c.tailmark, (size_t)rcount * N);
-            FC_HIP(hipMemsetAsync(tmark, 0, 4 * (size_t)rcount * N, c.stream));
-            if (c.trace) fprintf(stderr, "[fc] cd it=%d tail kernel from sweep %d\n", iteration, sweep);
-            k_list_fill<<<dim3(lb_grid, rcount), TB, 2 * sizeof(int) * B, c.stream>>>(a, sweep, gco, cursor, list);
-            if (!louv)
-                k_cd_tail<false, int32_t, TAIL_TB><<<rcount, TAIL_TB, 0, c.stream>>>(a, sweep, c.max_sweeps, tbuf, tmark, tail_acc, n_active);
-            else if (tot32)
-                k_cd_tail<true, int32_t, TAIL_TB><<<rcount, TAIL_TB, 0, c.stream>>>(a, sweep, c.max_sweeps, tbuf, tmark, tail_acc, n_active);
-            else
-                k_cd_tail<true, int64_t, TAIL_TB><<<rcount, TAIL_TB, 0, c.stream>>>(a, sweep, c.max_sweeps, tbuf, tmark, tail_acc, n_active);
-            if (c.trace) {
-                sync(c);
-                fprintf(stderr, "[fc] cd it=%d tail kernel dt_us=%.0f\n", iteration, trace_dt_us());
-            }
-            break;
+        if (!(tail_thr > 0 && (int64_t)hinfo[4] <= tail_thr && geo.B <= TAIL_MAXB)) return false;
+        int32_t* tbuf = ensure<int32_t>(c.tailbuf, (size_t)n_r * 3 * N);
+        int32_t* tmark = ensure<int32_t>(c.tailmark, (size_t)n_r * N);
+        FC_HIP(hipMemsetAsync(tmark, 0, 4 * (size_t)n_r * N, c.stream));
+        if (c.trace) fprintf(stderr, "[fc] cd it=%d tail kernel from sweep %d\n", iteration, sweep);
+        fill_list();
+        cd_dispatch(louv, tot32, [&](auto l, auto tt) {
+            k_cd_tail<l(), typename decltype(tt)::type, TAIL_TB><<<n_r, TAIL_TB, 0, c.stream>>>(a, sweep, c.max_sweeps, tbuf, tmark,
+                                                                                               tail_acc, n_active);
+        });
+        if (c.trace) {
+            sync(c);
+            fprintf(stderr, "[fc] cd it=%d tail kernel dt_us=%.0f\n", iteration, trace_dt_us());
         }
-        k_list_fill<<<dim3(lb_grid, rcount), TB, 2 * sizeof(int) * B, c.stream>>>(a, sweep, gco, cursor, list);
+        return true;
+    }
+
+    // One round (a bucket, or a coarse round of several): decide (light + heavy rows) against the
+    // state left by earlier rounds, apply.  Every grid is fixed and every size is read on the
+    // device, so a sweep never waits on the host.  X: decide item slots per replica.
+    template <bool LOUV, typename TT> void round(int k, int X) {
+        const int ev = timer_begin(c);
+        // one item per block: X item slots per replica, rounded up to whole XCD groups of 8
+        const int64_t grid = (((int64_t)a.n_r * X + 7) / 8) * 8;
+        k_decide_light<LOUV, TT><<<(unsigned)grid, DTB, 0, c.stream>>>(a, k, sweep, X);
+        timer_end(c, 4, ev);
+        if (hv) k_decide_heavy<LOUV, TT><<<HEAVY_GRID, TB, 0, c.stream>>>(a, k, sweep);
+        // apply: FC_APPLY_BLOCKS blocks per replica, more when few replicas share the GPU (a
+        // push/tracking move is a dependent row walk, so the chip needs ~2K resident blocks), but
+        // no more than the round's decisions fill (16-lane tiles)
+        const int64_t ab = std::min<int64_t>(std::max<int64_t>(c.apply_blocks, (2048 + a.n_r - 1) / a.n_r),
+                                             std::max<int64_t>(1, ((int64_t)X * LNT + TILES - 1) / TILES));
+        k_apply<LOUV, TT><<<dim3((unsigned)ab, a.n_r), ATB, 0, c.stream>>>(a, k);
+    }
+    void run_rounds() {
+        fill_list();
         const int X = std::max(hinfo[1], 1);
-        for (int k = 0; k < rounds; ++k) {
-            if (!louv) sub_round<false, int32_t>(c, a, k, sweep, hv, X);
-            else if (tot32) sub_round<true, int32_t>(c, a, k, sweep, hv, X);
-            else sub_round<true, int64_t>(c, a, k, sweep, hv, X);
-        }
+        cd_dispatch(louv, tot32, [&](auto l, auto tt) {
+            for (int k = 0; k < rounds; ++k) round<l(), typename decltype(tt)::type>(k, X);
+        });
+    }
+
+    void end_sweep() {
         if (a.lm) k_mark_lm<<<ig, TB, 0, c.stream>>>(a);
         if (louv) k_sweep_end<true><<<1, TB, 0, c.stream>>>(a, n_active);
         else k_sweep_end<false><<<1, TB, 0, c.stream>>>(a, n_active);
@@ -1595,37 +1626,55 @@ void cd_run(Ctx& c, int algo, int rbegin, int rcount, int n_p_total, int iterati
                     sweep, rounds, visits, *(unsigned long long*)(st4 + 2), st4[0], trace_dt_us());
         }
     }
-    // replica-sweeps and light-kernel traffic counters for the roofline model
-    std::vector<unsigned long long> sa(8 * (size_t)rcount + 4);   // sacc | n_active | tail_acc
-    FC_HIP(hipMemcpyAsync(sa.data(), sacc, sa.size() * 8, hipMemcpyDeviceToHost, c.stream));
-    sync(c);
-    const unsigned long long rep_sweeps = sa[4 * (size_t)rcount + 2];   // n_active[4..5]
-    if (c.trace)
-        fprintf(stderr, "[fc] cd it=%d done: %d multi-kernel sweeps, %.2f sweeps per replica\n", iteration, sweep,
-                (double)rep_sweeps / rcount);
-    if (!c.order_pass) {
-        c.acc.cd_sweeps += (int64_t)rep_sweeps;
-        c.prof.cd_sweeps += (int64_t)rep_sweeps;
+
+    // replica-sweeps and light-kernel traffic counters for the roofline model; the load-time
+    // ordering run (store_order) counts nothing
+    void statistics() {
+        std::vector<unsigned long long> sa(8 * (size_t)n_r + 4);   // sacc | n_active | tail_acc
+        FC_HIP(hipMemcpyAsync(sa.data(), a.sacc, sa.size() * 8, hipMemcpyDeviceToHost, c.stream));
+        sync(c);
+        const unsigned long long rep_sweeps = sa[4 * (size_t)n_r + 2];   // n_active[4..5]
+        if (c.trace)
+            fprintf(stderr, "[fc] cd it=%d done: %d multi-kernel sweeps, %.2f sweeps per replica\n", iteration, sweep,
+                    (double)rep_sweeps / n_r);
+        if (!c.order_pass) {
+            c.acc.cd_sweeps += (int64_t)rep_sweeps;
+            c.prof.cd_sweeps += (int64_t)rep_sweeps;
+        }
+        c.hpin[0] = c.hpin[1] = c.hpin[2] = 0;
+        int64_t tv = 0, te = 0;
+        for (int r = 0; r < n_r; ++r) {
+            c.hpin[0] += sa[4 * r]; c.hpin[1] += sa[4 * r + 1]; c.hpin[2] += sa[4 * r + 2];
+            tv += sa[4 * (size_t)n_r + 4 + 4 * r]; te += sa[4 * (size_t)n_r + 4 + 4 * r + 1];
+        }
+        // algorithmic bytes of the light decide kernel: per vertex rowptr 16 + kdeg 8 + own
+        // label 4 + own tot (4|8) + decision 8 + list entry 4; per adjacency entry neighbour
+        // label 4 + weight 4; per Sigma gathered (candidates of maximal val) its tot (4|8)
+        // (louvain).  LPA: no kdeg/tot/weights.
+        const int64_t tsz = tot32 ? 4 : 8;
+        const int64_t db = louv ? c.hpin[0] * (40 + tsz) + c.hpin[1] * 8 + c.hpin[2] * tsz
+                                : c.hpin[0] * 32 + c.hpin[1] * 4;
+        for (fc_stats* s : {&c.acc, &c.prof}) {
+            if (c.order_pass) break;
+            s->cd_vertex_visits += c.hpin[0] + tv;   // light kernel + tail kernel
+            s->cd_edge_visits += c.hpin[1] + te;
+            s->decide_bytes += db;                   // light kernel only (its time is decide_ms)
+        }
     }
-    c.hpin[0] = c.hpin[1] = c.hpin[2] = 0;
-    int64_t tv = 0, te = 0;
-    for (int r = 0; r < rcount; ++r) {
-        c.hpin[0] += sa[4 * r]; c.hpin[1] += sa[4 * r + 1]; c.hpin[2] += sa[4 * r + 2];
-        tv += sa[4 * (size_t)rcount + 4 + 4 * r]; te += sa[4 * (size_t)rcount + 4 + 4 * r + 1];
+};
+
+void cd_run(Ctx& c, int algo, int rbegin, int rcount, int n_p_total, int iteration, int shared_full,
+            const CDHandoff* h) {
+    FC_REQUIRE(rcount >= 1 && rbegin >= 0 && rbegin + rcount <= n_p_total, FC_EINVAL, "bad replica range");
+    FC_REQUIRE(c.N > 0 && c.g.rowptr.p, FC_ESTATE, "no graph loaded");
+    const int sl0 = timer_begin(c);
+    CdRun r(c, algo, rbegin, rcount, n_p_total, iteration, shared_full, h);
+    for (; r.sweep < c.max_sweeps && c.g.M2 > 0; ++r.sweep) {
+        if (!r.plan_sweep() || r.tail()) break;
+        r.run_rounds();
+        r.end_sweep();
     }
-    // algorithmic bytes of the light decide kernel: per vertex rowptr 16 + kdeg 8 + own
-    // label 4 + own tot (4|8) + decision 8 + list entry 4; per adjacency entry neighbour
-    // label 4 + weight 4; per Sigma gathered (candidates of maximal val) its tot (4|8)
-    // (louvain).  LPA: no kdeg/tot/weights.
-    const int64_t tsz = tot32 ? 4 : 8;
-    const int64_t db = louv ? c.hpin[0] * (40 + tsz) + c.hpin[1] * 8 + c.hpin[2] * tsz
-                            : c.hpin[0] * 32 + c.hpin[1] * 4;
-    for (fc_stats* s : {&c.acc, &c.prof}) {
-        if (c.order_pass) break;                 // load-time ordering run (store_order)
-        s->cd_vertex_visits += c.hpin[0] + tv;   // light kernel + tail kernel
-        s->cd_edge_visits += c.hpin[1] + te;
-        s->decide_bytes += db;                   // light kernel only (its time is decide_ms)
-    }
+    r.statistics();
     timer_end(c, 0, sl0);
 #ifdef FC_PHASE_PROF
     {

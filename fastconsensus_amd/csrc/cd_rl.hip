@@ -57,9 +57,6 @@ constexpr int RL_MAX_REPLICAS = 16384;
 #endif
 
 constexpr int32_t DONE = -1;            // merged / own / empty table entry (labels are >= 0)
-constexpr int NSH = 16;                 // counter shards per replica
-constexpr int RF = 8;                   // fields: 0 dq, 1 unstable, 2 moves, 3 visits, 4 entries, 5 cands, 6 units
-constexpr double DQ_SCALE = 1099511627776.0;   // 2^40 fixed point for predicted dQ (as cd.hip)
 constexpr int HWSLOTS = 1024;           // heavy rows: LDS table slots per wave (rows <= 512 entries)
 constexpr int HTB = 256;
 constexpr int HEAVY_GRID = 2048;       // k_rl_exact blocks at most (HTB / 64 visits each)
@@ -74,6 +71,22 @@ constexpr int LPER = 8;                 // vertices per thread in the list kerne
 constexpr int NCLS = 6;
 __host__ __device__ __forceinline__ int rl_class(int d) {
     return d <= 16 ? 0 : d <= 24 ? 1 : d <= 32 ? 2 : d <= 48 ? 3 : d <= DM ? 4 : 5;
+}
+// Degree classes -> decide launches (host): classes c0 .. c1 - 1 go to the sorting network of K
+// keys -- every light class on its own, or neighbouring classes merged into the wider network
+// (fewer, larger launches)
+struct ClsGroup { int c0, c1, K; };
+struct ClsGroups { const ClsGroup* g; int n; };
+constexpr ClsGroup G2[] = {{0, 3, 32}, {3, 5, 64}};   // in-kernel widths: one unit per wave, or FC_RL_SPLIT bits 8 and 16
+constexpr ClsGroup G3[] = {{0, 1, 16}, {1, 3, 32}, {3, 5, 64}};
+constexpr ClsGroup G4[] = {{0, 1, 16}, {1, 3, 32}, {3, 4, 48}, {4, 5, 64}};
+constexpr ClsGroup G5[] = {{0, 1, 16}, {1, 2, 24}, {2, 3, 32}, {3, 4, 48}, {4, 5, 64}};
+// gsel: Ctx::rl_groups_louv / rl_groups_lpa; u1: the one-unit-per-wave decide (rl_sorted_u1)
+inline ClsGroups rl_groups(int gsel, bool u1) {
+    if (gsel == 2 && (u1 || (FC_RL_SPLIT & 24) == 24)) return {G2, 2};
+    if (gsel <= 3) return {G3, 3};
+    if (gsel == 4) return {G4, 4};
+    return {G5, 5};
 }
 
 struct RL {
@@ -356,7 +369,7 @@ __device__ __forceinline__ Unit rl_unit(const RL& a, int64_t e0, int64_t e1, int
     u.valid = u.e < e1 && u.s < a.VPW;
     return u;
 }
-__device__ __forceinline__ int64_t rl_items(const RL& a, int64_t n) {
+__host__ __device__ __forceinline__ int64_t rl_items(const RL& a, int64_t n) {
     return a.banks == 1 ? (n + a.VPW - 1) / a.VPW : n * a.banks;
 }
 
@@ -1725,6 +1738,63 @@ void rl_handoff_fill(Ctx& c, const void* user, int32_t* lab, int32_t* tot, uint3
     }
 }
 
+// ------------------------------------------------------------------ driver: layouts, dispatch
+// The sweep plan (int32, Ctx::vcnt): boff [nseg+1] | voff [nseg+1] | n_active copy [2] | bcnt |
+// cursor | vcnt | vcursor [nseg each].  The first three are the sweep record, one pinned DMA
+// per sweep to 16 int32 past the pinned scratch's start.
+struct RlPlan {
+    int64_t nseg;
+    int64_t boff() const { return 0; }
+    int64_t voff() const { return nseg + 1; }
+    int64_t record_ints() const { return 2 * (nseg + 1) + 2; }
+    int64_t bcnt() const { return record_ints(); }
+    int64_t cursor() const { return bcnt() + nseg; }
+    int64_t vcnt() const { return cursor() + nseg; }
+    int64_t vcursor() const { return vcnt() + nseg; }
+    size_t ints() const { return 6 * (size_t)nseg + 16; }
+    bool record_fits() const { return 16 + record_ints() <= 2 * (int64_t)FC_HPIN_I64; }
+};
+// Per-replica state (bytes, Ctx::rl_state): active i32 [n_r] | track i32 [2 n_r] | (256-byte
+// aligned, zeroed as one run:) red u64 [n_r][NSH][RF] | sacc u64 [n_r][4] | n_active i32 [8]
+struct RlState {
+    size_t n_r;
+    size_t track() const { return 4 * n_r; }
+    size_t red() const { return (12 * n_r + 255) & ~size_t(255); }
+    size_t sacc() const { return red() + 8 * n_r * NSH * RF; }
+    size_t n_active() const { return sacc() + 32 * n_r; }
+    size_t zeroed() const { return n_active() + 32 - red(); }
+    size_t bytes() const { return n_r * (12 + 8 * NSH * RF + 32) + 512; }
+};
+// blocks of a grid-stride launch over `items` wave items
+inline unsigned rl_grid(int64_t items, int64_t cap = 8192) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, cap));
+}
+
+// f(LOUV) / f(LOUV, K, WM, U1) with the run-time values as compile-time constants, for the
+// kernels' template arguments: (LOUV, WM) is (true, UNIT | W8 | WIDE) or (false, UNIT), K the class
+// group's network width
+template <class F> void rl_dispatch(bool louv, F&& f) {
+    if (louv) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class L, class W, class F> void rl_dispatch_k(L l, W w, int K, bool u1, F&& f) {
+    auto k = [&](auto kk) {
+        if (u1) f(l, kk, w, std::true_type{});
+        else f(l, kk, w, std::false_type{});
+    };
+    if (K == 16) k(std::integral_constant<int, 16>{});
+    else if (K == 24) k(std::integral_constant<int, 24>{});
+    else if (K == 32) k(std::integral_constant<int, 32>{});
+    else if (K == 48) k(std::integral_constant<int, 48>{});
+    else k(std::integral_constant<int, 64>{});
+}
+template <class F> void rl_dispatch(bool louv, bool unitw, bool colw, int K, bool u1, F&& f) {
+    if (louv && unitw) rl_dispatch_k(std::true_type{}, std::integral_constant<int, WM_UNIT>{}, K, u1, f);
+    else if (louv && colw) rl_dispatch_k(std::true_type{}, std::integral_constant<int, WM_W8>{}, K, u1, f);
+    else if (louv) rl_dispatch_k(std::true_type{}, std::integral_constant<int, WM_WIDE>{}, K, u1, f);
+    else rl_dispatch_k(std::false_type{}, std::integral_constant<int, WM_UNIT>{}, K, u1, f);
+}
+
 }  // namespace
 
 // Replica-lane layout of a batch of n_r local replicas: lane group LG (power of two, 8..64),
@@ -1744,10 +1814,9 @@ static bool cd_rl_fits(const Ctx& c, int algo) {
     // consensus graph -- 2M past 2^31 at SBM-4M, n_p = 128 -- still fits its label propagation);
     // the sweep record (boff | voff | n_active, one pinned DMA per sweep) must fit the pinned
     // scratch: B * NCLS segments, i.e. B <= 339 buckets -- more go to cd.hip (same semantics)
-    const int64_t nseg = (int64_t)cd_buckets(c, algo) * NCLS;
+    const RlPlan plan{(int64_t)cd_buckets(c, algo) * NCLS};
     return !c.order_pass && (is_louvain(algo) || algo == FC_ALGO_LPM) && (!is_louvain(algo) || c.g.M2 <= 0x7fffffffll) &&
-           c.g.m < (int64_t(1) << 31) && (c.chunk == 0 || c.chunk == RL_CHUNK) &&
-           16 + 2 * (nseg + 1) + 2 <= 2 * (int64_t)FC_HPIN_I64;
+           c.g.m < (int64_t(1) << 31) && (c.chunk == 0 || c.chunk == RL_CHUNK) && plan.record_fits();
 }
 bool cd_rl_supported(const Ctx& c, int algo) { return c.cd_engine == 1 && cd_rl_fits(c, algo); }
 
@@ -1766,130 +1835,154 @@ void cd_run_hybrid(Ctx& c, int algo, int rbegin, int rcount, int n_p_total, int 
         cd_run(c, algo, rbegin, rcount, n_p_total, iteration, 1);
 }
 
-void cd_run_rl(Ctx& c, int algo, int rbegin, int rcount, int n_p_total, int iteration, bool hybrid) {
-    FC_REQUIRE(rcount >= 1 && rbegin >= 0 && rbegin + rcount <= n_p_total, FC_EINVAL, "bad replica range");
-    FC_REQUIRE(rcount <= RL_MAX_REPLICAS, FC_ELIMIT, "replica-lane engine: more than 16384 replicas per GPU");
-    FC_REQUIRE(c.N > 0 && c.g.rowptr.p, FC_ESTATE, "no graph loaded");
-    const int sl0 = timer_begin(c);
-    const bool louv = is_louvain(algo);
-    const int64_t N = c.N;
-    Graph& g = c.g;
-    c.n_r = rcount; c.rbase = rbegin; c.n_p_total = n_p_total;
+namespace {
+
+// The state of one cd_run_rl() run; its methods are the phases, in the order cd_run_rl() calls
+// them.  `a` outlives the loop: a hand-off reads it through CDHandoff::user.
+struct RlRun {
+    enum Next { GO, STOP, HAND_OVER };
+    Ctx& c;
+    Graph& g;
+    const bool louv, hybrid;
+    const int iteration, n_r;
+    const int64_t N;
     int LG, VPW, banks, ldT;
-    rl_layout(rcount, &LG, &VPW, &banks, &ldT);
-    const int CH = c.chunk;
-    const int64_t NC = CH ? (N + 2 * CH - 2) / CH : N;   // room for the chunk-grid shift (as cd.hip)
-    const int B = (int)std::min<int64_t>(cd_buckets(c, algo), NC);
-    const int64_t S = CH ? ((NC + B - 1) / B) * CH : (N + B - 1) / B;
-    const int64_t PN = CH ? NC * CH : N;
-
+    const SweepGeom geo;
+    const int nseg;              // segments of a sweep's list: bucket * NCLS + degree class
     RL a;
-    a.N = N; a.S = S; a.PN = PN; a.chunk = CH; a.perm_n = (uint32_t)NC; a.B = B;
-    a.n_r = rcount; a.rbase = rbegin; a.LG = LG; a.VPW = VPW; a.banks = banks; a.ldT = ldT;
-    a.lgs = 0;
-    while ((1 << a.lgs) < LG) ++a.lgs;
-    a.iter = (uint32_t)iteration; a.seed = c.seed;
-    a.rowptr = g.rowptr.as<int64_t>(); a.col = g.col.as<int32_t>(); a.cw = g.cw.as<int32_t>();
-    a.vrec = g.vrec.as<int4>(); a.kdeg = g.kdeg.as<int64_t>(); a.M2 = g.M2;
-    a.unitw = (!louv || (g.max_w == 1 && g.M2 == 2 * g.m)) ? 1 : 0;
-    a.wbits = 0;
-    while (a.wbits < 31 && ((int64_t)g.max_w >> a.wbits) != 0) ++a.wbits;
-    // sortable keys (label << wbits | weight) need N << wbits < 2^31; else the LDS merge
-    const bool pack = ((int64_t)(N - 1) << (a.unitw ? 0 : a.wbits)) < (int64_t(1) << 31);
-    a.colw = nullptr;
-    if (pack && louv && !a.unitw && a.wbits <= 8 && g.m > 0) {
-        int32_t* cwp = ensure<int32_t>(c.rl_colw, 2 * (size_t)g.m);
-        k_rl_colw<<<nb(2 * g.m, 256), 256, 0, c.stream>>>(2 * g.m, g.col.as<int32_t>(), g.cw.as<int32_t>(), a.wbits, cwp);
-        a.colw = cwp;
-    }
-    a.lab = ensure<int32_t>(c.labT, (size_t)N * ldT);
-    a.tot = louv ? ensure<int32_t>(c.rl_tot, (size_t)N * ldT) : nullptr;
-    a.dec = ensure<int32_t>(c.dec, (size_t)PN * ldT);
-    // slow visits of one bucket: at most its entries (<= S) times the local replicas
-    a.slow = ensure<int64_t>(c.rl_slow, (size_t)S * ldT + 1);
-    a.slow_cnt = ensure<int32_t>(c.rl_slow_cnt, 4);
-    FC_HIP(hipMemsetAsync(a.slow_cnt, 0, 4, c.stream));
-    a.list = (int4*)ensure<int4>(c.vlist, (size_t)PN);
-    a.lmask = (uint64_t*)ensure<uint64_t>(c.rl_lmask, (size_t)PN * banks);
-    a.vmask = (uint64_t*)ensure<uint64_t>(c.rl_vmask, (size_t)N * banks);
-    const int nseg = B * NCLS;
-    // boff [nseg+1] | voff [nseg+1] | n_active copy [2] | bcnt | cursor | vcnt | vcursor
-    int32_t* plan = ensure<int32_t>(c.vcnt, 6 * (size_t)nseg + 16);
-    a.boff = plan;
-    a.voff = a.boff + nseg + 1;
-    int32_t* bcnt = a.voff + nseg + 3;
-    a.cursor = bcnt + nseg;
-    int32_t* vcnt = a.cursor + nseg;
-    a.vcursor = vcnt + nseg;
-    FC_REQUIRE(16 + 2 * (nseg + 1) + 2 <= 2 * FC_HPIN_I64, FC_ELIMIT, "too many CD buckets for the pinned sweep record");
-    FC_HIP(hipMemsetAsync(bcnt, 0, sizeof(int32_t) * nseg, c.stream));   // kept zero by k_rl_list_plan
-    FC_HIP(hipMemsetAsync(vcnt, 0, sizeof(int32_t) * nseg, c.stream));
-    a.vlist = nullptr;
-    a.aff = (uint64_t*)ensure<uint64_t>(c.rl_aff, (size_t)banks * N);
-    a.mvf = (uint64_t*)ensure<uint64_t>(c.rl_mvf, (size_t)banks * N);
-    FC_HIP(hipMemsetAsync(a.aff, 0, 8 * (size_t)banks * N, c.stream));
-    FC_HIP(hipMemsetAsync(a.mvf, 0, 8 * (size_t)banks * N, c.stream));
-    a.prune = c.prune;
-    a.track_div = c.track_div;
-    // Leiden-style marks (cd.hip): consensus graphs, or every graph with prune_mark = 2
-    a.lm = ((g.max_w > 1 || c.prune_mark == 2) && c.prune && c.prune_mark >= 1) ? 1 : 0;
-    a.min_dq = c.cd_min_dq;
-    a.hybrid = hybrid ? 1 : 0;
-    int32_t* acnt = hybrid ? ensure<int32_t>(c.aff_cnt, (size_t)rcount) : nullptr;
-    a.acnt = acnt;
-    a.dense_div = c.dense_div;
-    // per-replica state: active i32 [n_r] | track i32 [2 n_r] | red u64 [n_r][NSH][RF] | sacc u64 [n_r][4] | n_active [8]
-    char* rs = (char*)ensure<char>(c.rl_state, (size_t)rcount * (12 + 8 * NSH * RF + 32) + 512);
-    a.active = (int32_t*)rs;
-    a.track = a.active + rcount;
-    a.red = (unsigned long long*)(rs + (((size_t)rcount * 12 + 255) & ~size_t(255)));
-    a.sacc = a.red + (size_t)rcount * NSH * RF;
-    int32_t* n_active = (int32_t*)(a.sacc + 4 * (size_t)rcount);
-    const size_t zero_bytes = (char*)(n_active + 8) - (char*)a.red;
-    FC_HIP(hipMemsetAsync(a.track, 0, 8 * (size_t)rcount, c.stream));
-    FC_HIP(hipMemsetAsync(a.red, 0, zero_bytes, c.stream));
-    {
-        std::vector<int32_t> ones(rcount, (g.M2 > 0) ? 1 : 0);
-        FC_HIP(hipMemcpyAsync(a.active, ones.data(), sizeof(int32_t) * rcount, hipMemcpyHostToDevice, c.stream));
-        sync(c);   // `ones` is pageable host memory
-    }
-    a.hslots = 1;
-    while (a.hslots < 2 * (int64_t)g.max_deg) a.hslots <<= 1;
-    a.hscratch = nullptr;
-    // global tables (rows past HWSLOTS / 2): one per wave of at most hblocks blocks, <= 1 GiB in all
-    int64_t hblocks = HEAVY_GRID;
-    if (a.hslots > HWSLOTS) {
-        hblocks = std::max<int64_t>(1, std::min<int64_t>(HEAVY_GRID, (int64_t(1) << 30) / ((HTB / 64) * 2 * a.hslots * 4)));
-        a.hscratch = ensure<int32_t>(c.heavy_scratch, (size_t)hblocks * (HTB / 64) * 2 * a.hslots);
-    }
-
-    k_rl_init<<<nb(N * ldT, 256), 256, 0, c.stream>>>(N, ldT, g.kdeg.as<int64_t>(), a.lab, a.tot);
-
-    int32_t* hb = (int32_t*)(c.hpin + 8);   // boff | voff | n_active[0..1] (pinned: one DMA per sweep)
-    int32_t* hinfo = hb + 2 * (nseg + 1);
-    const unsigned lgrid = nb(N, LTB * LPER);
-    const size_t lcount_lds = sizeof(unsigned long long) * 2 * banks + 2 * sizeof(int) * nseg;
+    bool pack;                   // sortable keys (label << wbits | weight): N << wbits < 2^31; else the LDS merge
+    int32_t *bcnt, *vcnt, *n_active, *acnt;
+    // the sweep record (pinned): boff | voff | hinfo: the active replicas the previous sweep
+    // left, the replicas whose filtered list is sparse (hybrid)
+    int32_t *hboff, *hvoff, *hinfo;
+    int64_t hblocks = HEAVY_GRID;   // k_rl_exact blocks at most
+    unsigned lgrid;              // list kernels
     int sweep = 0, handoff = -1;
-    if (c.trace) { sync(c); trace_dt_us(true); }
-    for (; sweep < c.max_sweeps && g.M2 > 0; ++sweep) {
+    // the current sweep's launch modes
+    bool vmode = false, u1 = false;
+    ClsGroups groups{};
+
+    int64_t entries(int seg, int ns = 1) const { return hboff[seg + ns] - hboff[seg]; }
+    int64_t visits(int seg, int ns = 1) const { return hvoff[seg + ns] - hvoff[seg]; }
+
+    // set-up: the batch's buffers, the launch arguments and the initial partition (singletons)
+    RlRun(Ctx& c_, int algo, int rbegin, int rcount, int n_p_total, int iteration_, bool hybrid_)
+        : c(c_), g(c_.g), louv(is_louvain(algo)), hybrid(hybrid_), iteration(iteration_), n_r(rcount), N(c_.N),
+          geo(c_, algo), nseg(geo.B * NCLS) {
+        c.n_r = rcount; c.rbase = rbegin; c.n_p_total = n_p_total;
+        rl_layout(rcount, &LG, &VPW, &banks, &ldT);
+        a.N = N; a.S = geo.S; a.PN = geo.PN; a.chunk = geo.CH; a.perm_n = (uint32_t)geo.NC; a.B = geo.B;
+        a.n_r = rcount; a.rbase = rbegin; a.LG = LG; a.VPW = VPW; a.banks = banks; a.ldT = ldT;
+        a.lgs = 0;
+        while ((1 << a.lgs) < LG) ++a.lgs;
+        a.iter = (uint32_t)iteration; a.seed = c.seed;
+        a.rowptr = g.rowptr.as<int64_t>(); a.col = g.col.as<int32_t>(); a.cw = g.cw.as<int32_t>();
+        a.vrec = g.vrec.as<int4>(); a.kdeg = g.kdeg.as<int64_t>(); a.M2 = g.M2;
+        a.unitw = cd_unit_weights(c, louv) ? 1 : 0;
+        a.wbits = 0;
+        while (a.wbits < 31 && ((int64_t)g.max_w >> a.wbits) != 0) ++a.wbits;
+        pack = ((int64_t)(N - 1) << (a.unitw ? 0 : a.wbits)) < (int64_t(1) << 31);
+        a.colw = nullptr;
+        if (pack && louv && !a.unitw && a.wbits <= 8 && g.m > 0) {
+            int32_t* cwp = ensure<int32_t>(c.rl_colw, 2 * (size_t)g.m);
+            k_rl_colw<<<nb(2 * g.m, 256), 256, 0, c.stream>>>(2 * g.m, g.col.as<int32_t>(), g.cw.as<int32_t>(), a.wbits, cwp);
+            a.colw = cwp;
+        }
+        a.lab = ensure<int32_t>(c.labT, (size_t)N * ldT);
+        a.tot = louv ? ensure<int32_t>(c.rl_tot, (size_t)N * ldT) : nullptr;
+        a.dec = ensure<int32_t>(c.dec, (size_t)geo.PN * ldT);
+        // slow visits of one bucket: at most its entries (<= S) times the local replicas
+        a.slow = ensure<int64_t>(c.rl_slow, (size_t)geo.S * ldT + 1);
+        a.slow_cnt = ensure<int32_t>(c.rl_slow_cnt, 4);
+        FC_HIP(hipMemsetAsync(a.slow_cnt, 0, 4, c.stream));
+        a.list = (int4*)ensure<int4>(c.vlist, (size_t)geo.PN);
+        a.lmask = (uint64_t*)ensure<uint64_t>(c.rl_lmask, (size_t)geo.PN * banks);
+        a.vmask = (uint64_t*)ensure<uint64_t>(c.rl_vmask, (size_t)N * banks);
+        const RlPlan pl{nseg};
+        int32_t* plan = ensure<int32_t>(c.vcnt, pl.ints());
+        a.boff = plan + pl.boff();
+        a.voff = plan + pl.voff();
+        bcnt = plan + pl.bcnt();
+        a.cursor = plan + pl.cursor();
+        vcnt = plan + pl.vcnt();
+        a.vcursor = plan + pl.vcursor();
+        FC_REQUIRE(pl.record_fits(), FC_ELIMIT, "too many CD buckets for the pinned sweep record");
+        FC_HIP(hipMemsetAsync(bcnt, 0, sizeof(int32_t) * nseg, c.stream));   // kept zero by k_rl_list_plan
+        FC_HIP(hipMemsetAsync(vcnt, 0, sizeof(int32_t) * nseg, c.stream));
+        a.vlist = nullptr;
+        a.aff = (uint64_t*)ensure<uint64_t>(c.rl_aff, (size_t)banks * N);
+        a.mvf = (uint64_t*)ensure<uint64_t>(c.rl_mvf, (size_t)banks * N);
+        FC_HIP(hipMemsetAsync(a.aff, 0, 8 * (size_t)banks * N, c.stream));
+        FC_HIP(hipMemsetAsync(a.mvf, 0, 8 * (size_t)banks * N, c.stream));
+        a.prune = c.prune;
+        a.track_div = c.track_div;
+        a.lm = cd_leiden_marks(c) ? 1 : 0;
+        a.min_dq = c.cd_min_dq;
+        a.hybrid = hybrid ? 1 : 0;
+        acnt = hybrid ? ensure<int32_t>(c.aff_cnt, (size_t)rcount) : nullptr;
+        a.acnt = acnt;
+        a.dense_div = c.dense_div;
+        const RlState st{(size_t)rcount};
+        char* rs = (char*)ensure<char>(c.rl_state, st.bytes());
+        a.active = (int32_t*)rs;
+        a.track = (int32_t*)(rs + st.track());
+        a.red = (unsigned long long*)(rs + st.red());
+        a.sacc = (unsigned long long*)(rs + st.sacc());
+        n_active = (int32_t*)(rs + st.n_active());
+        FC_HIP(hipMemsetAsync(a.track, 0, 8 * (size_t)rcount, c.stream));
+        FC_HIP(hipMemsetAsync(a.red, 0, st.zeroed(), c.stream));
+        {
+            std::vector<int32_t> ones(rcount, (g.M2 > 0) ? 1 : 0);
+            FC_HIP(hipMemcpyAsync(a.active, ones.data(), sizeof(int32_t) * rcount, hipMemcpyHostToDevice, c.stream));
+            sync(c);   // `ones` is pageable host memory
+        }
+        a.hslots = 1;
+        while (a.hslots < 2 * (int64_t)g.max_deg) a.hslots <<= 1;
+        a.hscratch = nullptr;
+        // global tables (rows past HWSLOTS / 2): one per wave of at most hblocks blocks, <= 1 GiB in all
+        if (a.hslots > HWSLOTS) {
+            hblocks = std::max<int64_t>(1, std::min<int64_t>(HEAVY_GRID, (int64_t(1) << 30) / ((HTB / 64) * 2 * a.hslots * 4)));
+            a.hscratch = ensure<int32_t>(c.heavy_scratch, (size_t)hblocks * (HTB / 64) * 2 * a.hslots);
+        }
+
+        k_rl_init<<<nb(N * ldT, 256), 256, 0, c.stream>>>(N, ldT, g.kdeg.as<int64_t>(), a.lab, a.tot);
+
+        hboff = (int32_t*)(c.hpin + 8);
+        hvoff = hboff + pl.voff();
+        hinfo = hboff + pl.record_ints() - 2;
+        lgrid = nb(N, LTB * LPER);
+        if (c.trace) { sync(c); trace_dt_us(true); }
+    }
+
+    // the sweep's list segments and visit counts, and the one host read of the sweep
+    Next plan_sweep() {
         const int listed = (c.prune && sweep > 0) ? 1 : 0;
         if (hybrid && listed) {   // per-replica list sizes: a sparse one hands the batch to cd.hip
-            FC_HIP(hipMemsetAsync(acnt, 0, sizeof(int32_t) * (size_t)rcount, c.stream));
+            FC_HIP(hipMemsetAsync(acnt, 0, sizeof(int32_t) * (size_t)n_r, c.stream));
             if (a.dense_div) k_rl_aff_count<<<lgrid, LTB, sizeof(int) * 64 * banks, c.stream>>>(a, acnt);
             k_rl_hand<<<1, 256, 0, c.stream>>>(a, n_active);
         }
+        const size_t lcount_lds = sizeof(unsigned long long) * 2 * banks + 2 * sizeof(int) * nseg;
         k_rl_list_count<<<lgrid, LTB, lcount_lds, c.stream>>>(a, sweep, listed, bcnt, vcnt);
         k_rl_list_plan<<<1, 64, 0, c.stream>>>(nseg, bcnt, a.boff, a.cursor, vcnt, a.voff, a.vcursor, n_active);
-        FC_HIP(hipMemcpyAsync(hb, a.boff, sizeof(int32_t) * (2 * (nseg + 1) + 2), hipMemcpyDeviceToHost, c.stream));
+        FC_HIP(hipMemcpyAsync(hboff, a.boff, sizeof(int32_t) * RlPlan{nseg}.record_ints(), hipMemcpyDeviceToHost,
+                              c.stream));
         sync(c);
-        if (sweep > 0 && hinfo[0] == 0) break;                      // every replica has stopped
-        if (hybrid && listed && hinfo[1] > 0) { handoff = sweep; break; }   // a sparse filtered list: cd.hip
-        if (hb[nseg] == 0) break;
+        if (sweep > 0 && hinfo[0] == 0) return STOP;                // every replica has stopped
+        if (hybrid && listed && hinfo[1] > 0) {                     // a sparse filtered list: cd.hip
+            handoff = sweep;
+            return HAND_OVER;
+        }
+        return entries(0, nseg) == 0 ? STOP : GO;
+    }
+
+    // the sweep's entries, its launch modes and (visit mode) its visits
+    void fill_lists() {
         k_rl_list_fill<<<lgrid, LTB, 2 * sizeof(int) * nseg, c.stream>>>(a, sweep);
         // visit mode when the replicas of an entry are mostly idle (few visits per listed entry):
         // a wave per entry would run mostly empty lanes
-        const int64_t n_ent = hb[nseg], n_vis = hb[2 * nseg + 1];
-        const bool vmode = pack && c.rl_visit_div > 0 && n_vis * c.rl_visit_div < n_ent * (int64_t)std::min(rcount, 64);
+        const int64_t n_ent = entries(0, nseg), n_vis = visits(0, nseg);
+        vmode = pack && c.rl_visit_div > 0 && n_vis * c.rl_visit_div < n_ent * (int64_t)std::min(n_r, 64);
         if (vmode) {
             a.vlist = ensure<int64_t>(c.rl_vlist, (size_t)n_vis + 1);
             int32_t* nvv = ensure<int32_t>(c.rl_vcount, 2 * (size_t)n_ent + 2);
@@ -1898,155 +1991,133 @@ void cd_run_rl(Ctx& c, int algo, int rbegin, int rcount, int n_p_total, int iter
             k_rl_visits_fill<<<nb(n_ent, LTB), LTB, 0, c.stream>>>(a, n_ent, nvv + n_ent + 1);
         }
         // one unit per wave: rows read as wave-uniform, an item ahead (rl_sorted_u1)
-        const bool u1 = VPW == 1 && c.rl_u1;
-        // degree classes -> decide launches (sorting-network widths): every class on its own,
-        // or neighbouring classes merged into the wider network (fewer, larger launches)
-        struct ClsGroup { int c0, c1, K; };
-        static const ClsGroup G2[] = {{0, 3, 32}, {3, 5, 64}};   // one unit per wave only (in-kernel widths)
-        static const ClsGroup G3[] = {{0, 1, 16}, {1, 3, 32}, {3, 5, 64}};
-        static const ClsGroup G4[] = {{0, 1, 16}, {1, 3, 32}, {3, 4, 48}, {4, 5, 64}};
-        static const ClsGroup G5[] = {{0, 1, 16}, {1, 2, 24}, {2, 3, 32}, {3, 4, 48}, {4, 5, 64}};
-        const int gsel = louv ? c.rl_groups_louv : c.rl_groups_lpa;
-        const bool g2 = gsel == 2 && (u1 || (FC_RL_SPLIT & 24) == 24);
-        const ClsGroup* groups = g2 ? G2 : gsel <= 3 ? G3 : gsel == 4 ? G4 : G5;
-        const int ngroups = g2 ? 2 : gsel <= 3 ? 3 : gsel == 4 ? 4 : 5;
-        auto grid_of = [&](int64_t n) {
-            const int64_t items = banks == 1 ? (n + VPW - 1) / VPW : n * banks;
-            return (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, 8192));
-        };
-        for (int k = 0; k < B; ++k) {
-            const int64_t nb_all = hb[(k + 1) * NCLS] - hb[k * NCLS];
-            if (nb_all <= 0) continue;
-            // each decide launch timed on its own (span 7: one span per launch, as rocprofv3 counts them)
-            if (pack && vmode) {
-                for (int gi = 0; gi < ngroups; ++gi) {
-                    const int seg = k * NCLS + groups[gi].c0, ns = groups[gi].c1 - groups[gi].c0, KG = groups[gi].K;
-                    const int64_t n = hb[nseg + 1 + seg + ns] - hb[nseg + 1 + seg];
-                    if (n <= 0) continue;
-                    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 63) / 64, 8192));
-#define RL_LAUNCH(L, KK, U) do { const int ev = timer_begin(c); k_rl_decide_v<L, KK, U><<<grid, RTB, 0, c.stream>>>(a, seg, ns, sweep); timer_end(c, 7, ev); } while (0)
-#define RL_LAUNCH_K(L, U)                                                                            \
-    do {                                                                                             \
-        if (KG == 16) RL_LAUNCH(L, 16, U); else if (KG == 24) RL_LAUNCH(L, 24, U);                   \
-        else if (KG == 32) RL_LAUNCH(L, 32, U); else if (KG == 48) RL_LAUNCH(L, 48, U);              \
-        else RL_LAUNCH(L, 64, U);                                                                    \
-    } while (0)
-                    if (louv && a.unitw) RL_LAUNCH_K(true, WM_UNIT);
-                    else if (louv && a.colw) RL_LAUNCH_K(true, WM_W8);
-                    else if (louv) RL_LAUNCH_K(true, WM_WIDE);
-                    else RL_LAUNCH_K(false, WM_UNIT);
-#undef RL_LAUNCH_K
-#undef RL_LAUNCH
-                }
-            } else if (pack) {
-                // a bucket's decide launches follow each other with nothing between them: the end
-                // event of one is the start event of the next (one event record per launch)
-                int chain_ev = -1;
-                for (int gi = 0; gi < ngroups; ++gi) {
-                    const int seg = k * NCLS + groups[gi].c0, ns = groups[gi].c1 - groups[gi].c0, KG = groups[gi].K;
-                    const int64_t n = hb[seg + ns] - hb[seg];
-                    if (n <= 0) continue;
-                    const int64_t items = banks == 1 ? (n + VPW - 1) / VPW : n * banks;
-#define RL_LAUNCH_1(L, KK, U, U1)                                                                                  \
-    do {                                                                                                           \
-        const unsigned grid = (c.rl_grid_mul > 0 && L)                                                             \
-            ? (unsigned)std::max<int64_t>(1, std::min<int64_t>(items, rl_decide_slots<L, KK, U, U1>() * c.rl_grid_mul)) \
-            : grid_of(n);                                                                                          \
-        const int ev = chain_ev >= 0 ? chain_ev : timer_begin(c);                                                  \
-        k_rl_decide<L, KK, U, U1><<<grid, RTB, 0, c.stream>>>(a, seg, ns, sweep);                                  \
-        const int ee = timer_end_ev(c, 7, ev);                                                                     \
-        if (c.timer_chain) chain_ev = ee;                                                                          \
-    } while (0)
-#define RL_LAUNCH(L, KK, U) do { if (u1) RL_LAUNCH_1(L, KK, U, true); else RL_LAUNCH_1(L, KK, U, false); } while (0)
-#define RL_LAUNCH_K(L, U)                                                                            \
-    do {                                                                                             \
-        if (KG == 16) RL_LAUNCH(L, 16, U); else if (KG == 24) RL_LAUNCH(L, 24, U);                   \
-        else if (KG == 32) RL_LAUNCH(L, 32, U); else if (KG == 48) RL_LAUNCH(L, 48, U);              \
-        else RL_LAUNCH(L, 64, U);                                                                    \
-    } while (0)
-                    if (louv && a.unitw) RL_LAUNCH_K(true, WM_UNIT);
-                    else if (louv && a.colw) RL_LAUNCH_K(true, WM_W8);
-                    else if (louv) RL_LAUNCH_K(true, WM_WIDE);
-                    else RL_LAUNCH_K(false, WM_UNIT);
-#undef RL_LAUNCH_K
-#undef RL_LAUNCH
-#undef RL_LAUNCH_1
-                }
-            } else {
-                const int64_t n = hb[k * NCLS + NCLS - 1] - hb[k * NCLS];
-                if (n > 0) {
-                    const int ev = timer_begin(c);
-                    if (louv) k_rl_decide_lds<true><<<grid_of(n), RTB, 0, c.stream>>>(a, k, sweep);
-                    else k_rl_decide_lds<false><<<grid_of(n), RTB, 0, c.stream>>>(a, k, sweep);
-                    timer_end(c, 7, ev);
-                }
-            }
-            // exact decisions: the heavy rows (one wave per (entry, replica) visit, HTB / 64 per
-            // block) and, louvain, the slow visits the decide launches listed (count on the device:
-            // a floor of SLOW_GRID blocks, idle ones return at once)
-            {
-                const int64_t hv = (int64_t)(hb[(k + 1) * NCLS] - hb[k * NCLS + NCLS - 1]) * rcount;
-                const int64_t want = (hv + HTB / 64 - 1) / (HTB / 64) + (louv && pack ? SLOW_GRID : 0);
-                const unsigned hgrid = (unsigned)std::min<int64_t>(hblocks, want);
-                if (hgrid > 0) {
-                    if (louv) k_rl_exact<true><<<hgrid, HTB, 0, c.stream>>>(a, k, sweep);
-                    else k_rl_exact<false><<<hgrid, HTB, 0, c.stream>>>(a, k, sweep);
-                }
-            }
-            if (louv) k_rl_apply<true><<<grid_of(nb_all), RTB, 0, c.stream>>>(a, k);
-            else k_rl_apply<false><<<grid_of(nb_all), RTB, 0, c.stream>>>(a, k);
+        u1 = VPW == 1 && c.rl_u1;
+        groups = rl_groups(louv ? c.rl_groups_louv : c.rl_groups_lpa, u1);
+    }
+
+    // the light rows of bucket k: one launch per class group, each timed on its own (span 7: one
+    // span per launch, as rocprofv3 counts them)
+    void decide_light(int k) {
+        if (!pack) {
+            const int64_t n = entries(k * NCLS, NCLS - 1);
+            if (n <= 0) return;
+            const int ev = timer_begin(c);
+            rl_dispatch(louv, [&](auto l) { k_rl_decide_lds<l()><<<rl_grid(rl_items(a, n)), RTB, 0, c.stream>>>(a, k, sweep); });
+            timer_end(c, 7, ev);
+            return;
         }
-        if (a.lm) {
-            const int64_t items = banks == 1 ? (N + VPW - 1) / VPW : N * banks;
-            k_rl_mark_lm<<<(unsigned)std::min<int64_t>(items, 8192), RTB, 0, c.stream>>>(a);
+        // wave mode: a bucket's decide launches follow each other with nothing between them, so the
+        // end event of one is the start event of the next (one event record per launch)
+        int chain_ev = -1;
+        for (int gi = 0; gi < groups.n; ++gi) {
+            const int seg = k * NCLS + groups.g[gi].c0, ns = groups.g[gi].c1 - groups.g[gi].c0;
+            const int64_t n = vmode ? visits(seg, ns) : entries(seg, ns);
+            if (n <= 0) continue;
+            if (vmode) {
+                const int ev = timer_begin(c);
+                rl_dispatch(louv, a.unitw, a.colw, groups.g[gi].K, false, [&](auto l, auto kk, auto w, auto) {
+                    k_rl_decide_v<l(), kk(), w()><<<rl_grid((n + 63) / 64), RTB, 0, c.stream>>>(a, seg, ns, sweep);
+                });
+                timer_end(c, 7, ev);
+                continue;
+            }
+            rl_dispatch(louv, a.unitw, a.colw, groups.g[gi].K, u1, [&](auto l, auto kk, auto w, auto u) {
+                const unsigned grid = (c.rl_grid_mul > 0 && l())
+                    ? rl_grid(rl_items(a, n), rl_decide_slots<l(), kk(), w(), u()>() * c.rl_grid_mul)
+                    : rl_grid(rl_items(a, n));
+                const int ev = chain_ev >= 0 ? chain_ev : timer_begin(c);
+                k_rl_decide<l(), kk(), w(), u()><<<grid, RTB, 0, c.stream>>>(a, seg, ns, sweep);
+                const int ee = timer_end_ev(c, 7, ev);
+                if (c.timer_chain) chain_ev = ee;
+            });
         }
-        if (louv) k_rl_sweep_end<true><<<1, 256, 0, c.stream>>>(a, n_active);
-        else k_rl_sweep_end<false><<<1, 256, 0, c.stream>>>(a, n_active);
+    }
+
+    // bucket k: decide against the state the earlier buckets left, apply
+    void bucket(int k) {
+        const int64_t nb_all = entries(k * NCLS, NCLS);
+        if (nb_all <= 0) return;
+        decide_light(k);
+        // exact decisions: the heavy rows (one wave per (entry, replica) visit, HTB / 64 per
+        // block) and, louvain, the slow visits the decide launches listed (count on the device:
+        // a floor of SLOW_GRID blocks, idle ones return at once)
+        const int64_t hv = entries(k * NCLS + NCLS - 1) * n_r;
+        const int64_t want = (hv + HTB / 64 - 1) / (HTB / 64) + (louv && pack ? SLOW_GRID : 0);
+        const unsigned hgrid = (unsigned)std::min<int64_t>(hblocks, want);
+        if (hgrid > 0) rl_dispatch(louv, [&](auto l) { k_rl_exact<l()><<<hgrid, HTB, 0, c.stream>>>(a, k, sweep); });
+        rl_dispatch(louv, [&](auto l) { k_rl_apply<l()><<<rl_grid(rl_items(a, nb_all)), RTB, 0, c.stream>>>(a, k); });
+    }
+
+    void end_sweep() {
+        if (a.lm) k_rl_mark_lm<<<rl_grid(rl_items(a, N)), RTB, 0, c.stream>>>(a);
+        rl_dispatch(louv, [&](auto l) { k_rl_sweep_end<l()><<<1, 256, 0, c.stream>>>(a, n_active); });
         if (c.trace) {
             sync(c);
             int32_t st8[8];
             FC_HIP(hipMemcpy(st8, n_active, sizeof(st8), hipMemcpyDeviceToHost));
             fprintf(stderr, "[fc] rl it=%d sweep=%d entries=%d visits=%llu moves=%llu active=%d dt_us=%.0f\n", iteration,
-                    sweep, hb[nseg], *(unsigned long long*)(st8 + 6), *(unsigned long long*)(st8 + 2), st8[0],
+                    sweep, (int)entries(0, nseg), *(unsigned long long*)(st8 + 6), *(unsigned long long*)(st8 + 2), st8[0],
                     trace_dt_us());
         }
     }
-    if (handoff < 0) {
-        // labels for the consensus kernels (labT, native) and the slot-order rows everything else reads
-        int32_t* lab = ensure<int32_t>(c.lab, (size_t)rcount * N);
-        k_rl_export<<<dim3(nb(N, 64), (rcount + 63) / 64), 256, 0, c.stream>>>(N, rcount, ldT, a.lab, c.sinv.as<int32_t>(), lab);
+
+    // labels for the consensus kernels (labT, native) and the slot-order rows everything else reads
+    void export_labels() {
+        int32_t* lab = ensure<int32_t>(c.lab, (size_t)n_r * N);
+        k_rl_export<<<dim3(nb(N, 64), (n_r + 63) / 64), 256, 0, c.stream>>>(N, n_r, ldT, a.lab, c.sinv.as<int32_t>(), lab);
         c.ldT = ldT;
         c.labT_valid = true;
     }
-    // statistics: replica-sweeps, visits, and the decide kernel's algorithmic bytes
-    std::vector<unsigned long long> sa(4 * (size_t)rcount + 4);
-    FC_HIP(hipMemcpyAsync(sa.data(), a.sacc, sa.size() * 8, hipMemcpyDeviceToHost, c.stream));
-    sync(c);
-    const unsigned long long rep_sweeps = sa[4 * (size_t)rcount + 2];
-    unsigned long long vis = 0, ent = 0, cand = 0, units = 0;
-    for (int r = 0; r < rcount; ++r) { vis += sa[4 * r]; ent += sa[4 * r + 1]; cand += sa[4 * r + 2]; units += sa[4 * r + 3]; }
-    if (c.trace)
-        fprintf(stderr, "[fc] rl it=%d done: %d sweeps, %.2f sweeps per replica, %llu visits in %llu units\n", iteration,
-                sweep, (double)rep_sweeps / rcount, vis, units);
-    // algorithmic bytes of the light decide kernel: per unit (vertex x bank) its record 16 B
-    // and row (col 4 B, weight 4 B unless unit) per entry -- read once for every replica of
-    // the unit; per visit (vertex x replica) its own label 4 + own total 4 + decision 4, the
-    // neighbour labels 4 B per entry, and per Sigma gathered 4 B (louvain)
-    const unsigned long long rowb = a.unitw ? 4 : 8;
-    const unsigned long long db = louv ? units * 16 + (ent / std::max<unsigned long long>(1, vis)) * units * rowb +
-                                             vis * 12 + ent * 4 + cand * 4
-                                       : units * 16 + (ent / std::max<unsigned long long>(1, vis)) * units * rowb +
-                                             vis * 8 + ent * 4;
-    for (fc_stats* s : {&c.acc, &c.prof}) {
-        s->cd_sweeps += (int64_t)rep_sweeps;
-        s->cd_vertex_visits += (int64_t)vis;
-        s->cd_edge_visits += (int64_t)ent;
-        s->rl_decide_bytes += (int64_t)db;
+
+    // replica-sweeps, visits, and the decide kernel's algorithmic bytes
+    void statistics() {
+        std::vector<unsigned long long> sa(4 * (size_t)n_r + 4);
+        FC_HIP(hipMemcpyAsync(sa.data(), a.sacc, sa.size() * 8, hipMemcpyDeviceToHost, c.stream));
+        sync(c);
+        const unsigned long long rep_sweeps = sa[4 * (size_t)n_r + 2];
+        unsigned long long vis = 0, ent = 0, cand = 0, units = 0;
+        for (int r = 0; r < n_r; ++r) { vis += sa[4 * r]; ent += sa[4 * r + 1]; cand += sa[4 * r + 2]; units += sa[4 * r + 3]; }
+        if (c.trace)
+            fprintf(stderr, "[fc] rl it=%d done: %d sweeps, %.2f sweeps per replica, %llu visits in %llu units\n", iteration,
+                    sweep, (double)rep_sweeps / n_r, vis, units);
+        // algorithmic bytes of the light decide kernel: per unit (vertex x bank) its record 16 B
+        // and row (col 4 B, weight 4 B unless unit) per entry -- read once for every replica of
+        // the unit; per visit (vertex x replica) its own label 4 + own total 4 + decision 4, the
+        // neighbour labels 4 B per entry, and per Sigma gathered 4 B (louvain)
+        const unsigned long long rowb = a.unitw ? 4 : 8;
+        const unsigned long long db = louv ? units * 16 + (ent / std::max<unsigned long long>(1, vis)) * units * rowb +
+                                                 vis * 12 + ent * 4 + cand * 4
+                                           : units * 16 + (ent / std::max<unsigned long long>(1, vis)) * units * rowb +
+                                                 vis * 8 + ent * 4;
+        for (fc_stats* s : {&c.acc, &c.prof}) {
+            s->cd_sweeps += (int64_t)rep_sweeps;
+            s->cd_vertex_visits += (int64_t)vis;
+            s->cd_edge_visits += (int64_t)ent;
+            s->rl_decide_bytes += (int64_t)db;
+        }
     }
+};
+
+}  // namespace
+
+void cd_run_rl(Ctx& c, int algo, int rbegin, int rcount, int n_p_total, int iteration, bool hybrid) {
+    FC_REQUIRE(rcount >= 1 && rbegin >= 0 && rbegin + rcount <= n_p_total, FC_EINVAL, "bad replica range");
+    FC_REQUIRE(rcount <= RL_MAX_REPLICAS, FC_ELIMIT, "replica-lane engine: more than 16384 replicas per GPU");
+    FC_REQUIRE(c.N > 0 && c.g.rowptr.p, FC_ESTATE, "no graph loaded");
+    const int sl0 = timer_begin(c);
+    RlRun r(c, algo, rbegin, rcount, n_p_total, iteration, hybrid);
+    for (; r.sweep < c.max_sweeps && c.g.M2 > 0; ++r.sweep) {
+        if (r.plan_sweep() != RlRun::GO) break;
+        r.fill_lists();
+        for (int k = 0; k < r.a.B; ++k) r.bucket(k);
+        r.end_sweep();
+    }
+    if (r.handoff < 0) r.export_labels();
+    r.statistics();
     timer_end(c, 0, sl0);
-    if (handoff >= 0) {
-        if (c.trace) fprintf(stderr, "[fc] rl it=%d hands over to cd.hip at sweep %d\n", iteration, handoff);
-        const CDHandoff h{handoff, rl_handoff_fill, &a};
+    if (r.handoff >= 0) {   // r.a stays alive: rl_handoff_fill reads it through h.user
+        if (c.trace) fprintf(stderr, "[fc] rl it=%d hands over to cd.hip at sweep %d\n", iteration, r.handoff);
+        const CDHandoff h{r.handoff, rl_handoff_fill, &r.a};
         cd_run(c, algo, rbegin, rcount, n_p_total, iteration, 1, &h);
     }
 }

@@ -302,6 +302,34 @@ inline int closure_blocks(const Ctx& c) {
 inline int cd_buckets(const Ctx& c, int algo) {
     return c.buckets > 0 ? c.buckets : (is_louvain(algo) ? CD_BUCKETS_LOUVAIN : CD_BUCKETS_LPA);
 }
+// What cd.hip and cd_rl.hip must agree on: a hybrid batch starts on one and ends on the other
+// (CDHandoff), and the CPU twin reproduces both.
+// Per-replica sweep counters: NSH shards of RF u64 fields -- 0 dq, 1 unstable, 2 moves, 3 visits,
+// 4 entries, 5 cands, 6 units (cd_rl.hip only); the predicted dQ in 2^40 fixed point
+constexpr int NSH = 16;
+constexpr int RF = 8;
+constexpr double DQ_SCALE = 1099511627776.0;
+// Sweep positions: the vertices in a random order, or (chunk > 0) whole chunks of `chunk`
+// consecutive vertices in a random chunk order (coalesced per-vertex accesses).  NC positions
+// are permuted (chunks: with room for the chunk-grid shift), B buckets of S vertices each cover
+// the PN vertex positions.
+struct SweepGeom {
+    int CH, B;
+    int64_t NC, S, PN;
+    SweepGeom(const Ctx& c, int algo) : CH(c.chunk) {
+        NC = CH ? (c.N + 2 * CH - 2) / CH : c.N;
+        B = (int)(cd_buckets(c, algo) < NC ? cd_buckets(c, algo) : NC);
+        S = CH ? ((NC + B - 1) / B) * CH : (c.N + B - 1) / B;
+        PN = CH ? NC * CH : c.N;
+    }
+};
+// Leiden-style marks (a tracked sweep flags the neighbours that ended in another community than
+// the mover, not every neighbour): on consensus graphs, or on every graph with prune_mark = 2
+inline bool cd_leiden_marks(const Ctx& c) {
+    return (c.g.max_w > 1 || c.prune_mark == 2) && c.prune && c.prune_mark >= 1;
+}
+// every edge weighs 1 to the decide kernels: LPA ignores the weights, Louvain needs 2M = 2m
+inline bool cd_unit_weights(const Ctx& c, bool louv) { return !louv || (c.g.max_w == 1 && c.g.M2 == 2 * c.g.m); }
 
 // graph.cpp
 void graph_load(Ctx& c, int64_t n, int64_t m, const int32_t* u, const int32_t* v);

@@ -339,8 +339,11 @@ __global__ __launch_bounds__(256) void k_sc_emit(int64_t k, const int64_t* __res
         }
     }
 }
-// One run = one contingency cell of n members.  acc[f * LP + lane], f = 0..2 (sum n^2, cells,
-// sum n ln n as a double): LDS per block, then one global atomic per touched lane and field.
+// One run = one contingency cell of n members.  acc[f * LP + lane], f = 0..3 (sum n^2, cells, and
+// sum n ln n in fixed point: floor(x * 2^26) and the next 26 bits): LDS per block, then one global
+// atomic per touched lane and field.  A term x = n ln n >= 2 ln 2 is a whole multiple of 2^-52, so
+// the two integers hold it exactly, and integer sums do not depend on the order the atomics land
+// in: the same labelings give the same s_log in every run.  Up to 2^31 terms of sum < 2^36 fit.
 __global__ __launch_bounds__(256) void k_sc_fold(const int32_t* __restrict__ nruns,
                                                  const unsigned long long* __restrict__ ukeys,
                                                  const int32_t* __restrict__ counts, int64_t k, int LP,
@@ -348,8 +351,9 @@ __global__ __launch_bounds__(256) void k_sc_fold(const int32_t* __restrict__ nru
     extern __shared__ unsigned long long s_fold[];
     unsigned long long* s_sq = s_fold;
     unsigned long long* s_ce = s_fold + LP;
-    double* s_lg = reinterpret_cast<double*>(s_fold + 2 * LP);
-    for (int t = threadIdx.x; t < LP; t += blockDim.x) { s_sq[t] = 0; s_ce[t] = 0; s_lg[t] = 0.0; }
+    unsigned long long* s_l1 = s_fold + 2 * LP;
+    unsigned long long* s_l2 = s_fold + 3 * LP;
+    for (int t = threadIdx.x; t < LP; t += blockDim.x) { s_sq[t] = 0; s_ce[t] = 0; s_l1[t] = 0; s_l2[t] = 0; }
     __syncthreads();
     const int64_t n = *nruns;
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
@@ -360,14 +364,19 @@ __global__ __launch_bounds__(256) void k_sc_fold(const int32_t* __restrict__ nru
         const unsigned long long c = (unsigned long long)counts[j];
         atomicAdd(&s_sq[t], c * c);
         atomicAdd(&s_ce[t], 1ull);
-        if (c > 1) atomicAdd(&s_lg[t], (double)c * log((double)c));
+        if (c > 1) {
+            const double x26 = (double)c * log((double)c) * 67108864.0, f = floor(x26);
+            atomicAdd(&s_l1[t], (unsigned long long)f);
+            atomicAdd(&s_l2[t], (unsigned long long)((x26 - f) * 67108864.0));
+        }
     }
     __syncthreads();
     for (int t = threadIdx.x; t < LP; t += blockDim.x) {
         if (!s_ce[t]) continue;
         atomicAdd(&acc[t], s_sq[t]);
         atomicAdd(&acc[LP + t], s_ce[t]);
-        atomicAdd(reinterpret_cast<double*>(acc) + 2 * LP + t, s_lg[t]);
+        atomicAdd(&acc[2 * LP + t], s_l1[t]);
+        atomicAdd(&acc[3 * LP + t], s_l2[t]);
     }
 }
 static void score_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned long long* ovf, unsigned long long* acc) {
@@ -380,6 +389,7 @@ static void score_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned lon
     const int64_t T = read_i64(c, E + nbk);
     if (T == 0) return;
     FC_REQUIRE(nbk * 64 < ((int64_t)1 << 32), FC_ELIMIT, "too many (community, replica) slots for the scoring fallback");
+    FC_REQUIRE((size_t)LP * 32 <= 65536, FC_ELIMIT, "too many replicas for the scoring fallback's LDS table");
     const int64_t cap = std::max<int64_t>(2 * N, c.score_chunk), step = cap - N;
     unsigned long long* k1 = (unsigned long long*)ensure<uint64_t>(c.sc_fk1, cap);
     unsigned long long* k2 = (unsigned long long*)ensure<uint64_t>(c.sc_fk2, cap);
@@ -393,7 +403,7 @@ static void score_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned lon
         k_sc_emit<<<SC_GRID, TB, 0, c.stream>>>(s.k, rng, E, ovf, s.seg, s.sval, c.labT.as<int32_t>(), c.ldT, lo, hi, k1);
         sort_keys_public(c, (const uint64_t*)k1, (uint64_t*)k2, n, 64);
         run_length(c, (const unsigned long long*)k2, k1, rc, nr, n);
-        k_sc_fold<<<std::min<unsigned>(nblk(n), 1024u), TB, (size_t)LP * 24, c.stream>>>(nr, k1, rc, s.k, LP, acc);
+        k_sc_fold<<<std::min<unsigned>(nblk(n), 1024u), TB, (size_t)LP * 32, c.stream>>>(nr, k1, rc, s.k, LP, acc);
     }
 }
 
@@ -426,21 +436,21 @@ static void score_row_pairs(Ctx& c, const ScSeg& s, const std::vector<unsigned l
     FC_HIP(hipMemcpyAsync(dwant, hw, sizeof(uint64_t) * banks, hipMemcpyHostToDevice, c.stream));
     unsigned long long* ovf = (unsigned long long*)ensure<uint64_t>(c.sc_ovf, (size_t)banks * s.k + 1);
     unsigned long long* part = (unsigned long long*)ensure<uint64_t>(c.sc_part2, (size_t)banks * gx * 256);
-    unsigned long long* res = (unsigned long long*)ensure<uint64_t>(c.sc_res, (size_t)7 * LP);
-    FC_HIP(hipMemsetAsync(res + 4 * LP, 0, sizeof(uint64_t) * 3 * LP, c.stream));
+    unsigned long long* res = (unsigned long long*)ensure<uint64_t>(c.sc_res, (size_t)8 * LP);
+    FC_HIP(hipMemsetAsync(res + 4 * LP, 0, sizeof(uint64_t) * 4 * LP, c.stream));
     const int lcap = c.score_slow ? 0 : c.score_lcap;
     k_sc_pairs<<<dim3(gx, banks), TB, 0, c.stream>>>(s.k, s.seg, s.sval, c.labT.as<int32_t>(), c.ldT, c.n_r, dwant, lcap,
                                                      ovf, part);
     k_sc_pair_reduce<<<banks, 1024, 0, c.stream>>>(gx, LP, part, res);
     score_fallback(c, s, banks, ovf, res + 4 * LP);
-    std::vector<unsigned long long> h((size_t)7 * LP);
+    std::vector<unsigned long long> h((size_t)8 * LP);
     FC_HIP(hipMemcpyAsync(h.data(), res, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, c.stream));
     sync(c);
     out.assign(c.n_r, ScLane{});
     for (int r = 0; r < c.n_r; ++r) {
-        double l0, l1;
+        double l0;
         memcpy(&l0, &h[3 * LP + r], 8);
-        memcpy(&l1, &h[6 * LP + r], 8);
+        const double l1 = (double)(ldexpl((long double)h[6 * LP + r], -26) + ldexpl((long double)h[7 * LP + r], -52));
         out[r].sum_sq = (int64_t)(h[r] + h[4 * LP + r]);
         out[r].cells = (int64_t)(h[LP + r] + h[5 * LP + r]);
         out[r].slow = (int64_t)h[2 * LP + r];

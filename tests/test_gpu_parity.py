@@ -7,6 +7,7 @@ import pytest
 
 from oracle import oracle as orc
 from tests import golden_io
+from tests.twin_graph import internal_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -287,12 +288,7 @@ def test_cd_hybrid_dense_lists_bit_exact_vs_twin(fcmod, algo, dense_div, engine)
     case, eng = _weighted_consensus_engine(fcmod, 59)
     kw = _engine(eng, engine, 0, 8)
     eng.set_option("dense_div", dense_div)
-    u, v, w, _ = eng.get_graph()
-    sigma = eng.node_map()
-    a_, b_ = sigma[u], sigma[v]
-    lo, hi = np.minimum(a_, b_), np.maximum(a_, b_)
-    o = np.lexsort((hi, lo))
-    g_int = orc.EdgeGraph(case.N, lo[o], hi[o], w[o], np.zeros(len(o), np.int64))
+    g_int, sigma = internal_graph(eng, case.N)
     eng.cd(algo, 0, 12, 12, 6)
     exp, _ = orc.engine_cd(algo, g_int, 12, 0, 6, 59, dense_div=dense_div, **kw)
     np.testing.assert_array_equal(eng.get_labels(12), exp[:, sigma])
@@ -336,12 +332,7 @@ def test_cd_replica_lanes_visit_mode_bit_exact(fcmod, algo, visit_div, n_r, monk
     eng.close()
     case, eng = _weighted_consensus_engine(fcmod, 47)
     eng.set_option("cd_engine", 1)
-    u, v, w, _ = eng.get_graph()
-    sigma = eng.node_map()
-    a_, b_ = sigma[u], sigma[v]
-    lo, hi = np.minimum(a_, b_), np.maximum(a_, b_)
-    o = np.lexsort((hi, lo))
-    g_int = orc.EdgeGraph(case.N, lo[o], hi[o], w[o], np.zeros(len(o), np.int64))
+    g_int, sigma = internal_graph(eng, case.N)
     eng.cd(algo, 0, n_r, n_r, 3)
     exp, _ = orc.engine_cd(algo, g_int, n_r, 0, 3, 47, shared=1, coarsen=0)
     np.testing.assert_array_equal(eng.get_labels(n_r), exp[:, sigma])
@@ -441,12 +432,7 @@ def test_cd_replica_lanes_class_groups_bit_exact(fcmod, algo, n_r, groups, monke
     eng.close()
     case, eng = _weighted_consensus_engine(fcmod, 73)
     eng.set_option("cd_engine", 1)
-    u, v, w, _ = eng.get_graph()
-    sigma = eng.node_map()
-    a_, b_ = sigma[u], sigma[v]
-    lo, hi = np.minimum(a_, b_), np.maximum(a_, b_)
-    o = np.lexsort((hi, lo))
-    g_int = orc.EdgeGraph(case.N, lo[o], hi[o], w[o], np.zeros(len(o), np.int64))
+    g_int, sigma = internal_graph(eng, case.N)
     eng.cd(algo, 0, n_r, n_r, 3)
     exp, _ = orc.engine_cd(algo, g_int, n_r, 0, 3, 73, shared=1, coarsen=0)
     np.testing.assert_array_equal(eng.get_labels(n_r), exp[:, sigma])
@@ -474,13 +460,8 @@ def test_cd_replica_lanes_wide_weights_bit_exact(fcmod, n_r, u1, monkeypatch):
     eng.closure_partial(cnt)
     eng.closure_apply(0, n_w, case.delta, cnt, 0)
     eng.set_option("cd_engine", 1)
-    u, v, w, _ = eng.get_graph()
-    assert w.max() >= 256, "no weight past 8 bits"
-    sigma = eng.node_map()
-    a_, b_ = sigma[u], sigma[v]
-    lo, hi = np.minimum(a_, b_), np.maximum(a_, b_)
-    o = np.lexsort((hi, lo))
-    g_int = orc.EdgeGraph(case.N, lo[o], hi[o], w[o], np.zeros(len(o), np.int64))
+    assert eng.get_graph()[2].max() >= 256, "no weight past 8 bits"
+    g_int, sigma = internal_graph(eng, case.N)
     eng.cd(0, 0, n_r, n_r, 3)
     exp, _ = orc.engine_cd(0, g_int, n_r, 0, 3, 53, shared=1, coarsen=0)
     np.testing.assert_array_equal(eng.get_labels(n_r), exp[:, sigma])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
+from tests.twin_graph import internal_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -66,16 +67,6 @@ def _degrees(eng):
     return np.bincount(np.concatenate([u, v]), minlength=N)
 
 
-def _internal_graph(eng):
-    """The engine's working graph on its internal numbering, as the twin reads it."""
-    u, v, w, _ = eng.get_graph()
-    sigma = eng.node_map()
-    a_, b_ = sigma[u], sigma[v]
-    lo, hi = np.minimum(a_, b_), np.maximum(a_, b_)
-    o = np.lexsort((hi, lo))
-    return orc.EdgeGraph(N, lo[o], hi[o], w[o], np.zeros(len(o), np.int64)), sigma
-
-
 def _unit_engine(fcmod):
     eng = fcmod.Engine(seed=SEED)
     eng.set_option("cd_engine", 1)
@@ -115,7 +106,7 @@ def _twin(eng, algo, n_r, weighted, iteration):
     key = (algo, n_r, weighted)
     if key not in _expected:
         if weighted:
-            g_int, sigma = _internal_graph(eng)
+            g_int, sigma = internal_graph(eng, N)
         else:                                      # the input graph, deduplicated as the engine does
             sigma = eng.node_map()
             g_int = orc.EdgeGraph.from_lines(N, np.stack([sigma[EDGES[:, 0]], sigma[EDGES[:, 1]]], 1))

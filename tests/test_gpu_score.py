@@ -6,6 +6,7 @@ entropy and mi within the bound, nmi within bound / mean entropy where that is >
 modularity and ari within 1e-15 of the exact rational rounded once.
 """
 import json
+import math
 import os
 import subprocess
 import sys
@@ -266,6 +267,50 @@ def test_weighted_graph_and_forced_fallback(fcmod, lfr):
     assert auto["slow"] != slow["slow"]
     for k in ("working", "input", "pairs"):
         assert slow[k] == auto[k], k
+
+
+def _long_community_rows(n):
+    """Row 0: three communities, each longer than FC_SCORE_LCAP, so every pair with it goes through
+    the fallback.  Rows 1..7: 10..16 labels inside each of them, in cells of a few hundred members up to
+    ~0.7 n / 3 members (n ln n from ~1e3 to ~5e5: the fixed point's integer and fraction parts both in use)."""
+    i = np.arange(n, dtype=np.int64)
+    span = n // 3 + 1
+    a = i // span
+    frac = (i % span) / span
+    return np.stack([a] + [a * 64 + np.floor((9 + r) * frac ** (1 + r)).astype(np.int64) for r in range(1, 8)])
+
+
+def test_fallback_log_sum_exact_in_any_order(fcmod, monkeypatch):
+    """The fallback adds its n ln n terms exactly, so s_log, mi and nmi do not depend on the order
+    or the grouping of the additions: one key chunk per row (default) and eight of them
+    (FC_SCORE_CHUNK=1: 2 n keys each, other blocks and launches for the same runs) agree bit for
+    bit, and s_log is the exact sum of its terms up to the logarithms' own rounding (2 ulps per
+    term and one for the result: 2^-50 relative, against float_bound's 4 n 2^-53 ln n)."""
+    n = 200_003
+    rows = _long_community_rows(n)
+    u = np.arange(n - 1, dtype=np.int32)
+    pairs = [(0, r) for r in range(1, 8)]
+    recs = []
+    for chunk in (None, "1"):
+        if chunk:
+            monkeypatch.setenv("FC_SCORE_CHUNK", chunk)
+        with fcmod.Engine(seed=1) as eng:
+            eng.load_graph(n, u, u + 1)
+            eng.set_labels(rows)
+            recs.append(eng.score_pairs(pairs))
+    one, many = recs
+    assert (one["slow_members"] == n).all() and (many["slow_members"] == n).all()
+    largest, smallest = 0, n
+    for x in one:
+        check_pair(x, rows[0], rows[x["b"]], n)
+        cnt = np.unique(rows[0] * (1 << 20) + rows[x["b"]], return_counts=True)[1]
+        exact = math.fsum(float(c) * math.log(float(c)) for c in cnt if c > 1)
+        largest, smallest = max(largest, int(cnt.max())), min(smallest, int(cnt.min()))
+        print("pair", int(x["b"]), "s_log", x["s_log"], "exact", exact, "rel", abs(x["s_log"] - exact) / exact)
+        assert abs(x["s_log"] - exact) <= 2.0 ** -50 * exact
+    assert largest > 40_000 and smallest < 1000      # the inputs: long and short cells
+    for f in ("s_log", "mi", "nmi", "ari", "cells", "sum_sq"):
+        assert np.array_equal(one[f], many[f]), f
 
 
 # ------------------------------------------------------------------ 6. read-only
