@@ -33,6 +33,7 @@ SYMBOLS = [
     "fc_score_set_reference", "fc_score_partitions", "fc_score_pairs",
     "fc_consensus_support", "fc_consensus_partition", "fc_consensus_timing",
     "fc_consensus_levels", "fc_consensus_cut", "fc_consensus_levels_timing",
+    "fc_coassociation", "fc_coassoc_pairs", "fc_coassoc_hist", "fc_coassoc_timing",
 ]
 FC_SCORE_REF = -1
 SCORE_GRAPHS = {"input": 0, "working": 1}
@@ -165,6 +166,10 @@ def load():
     L.fc_consensus_levels.argtypes = [vp, c_int, vp, c_int, vp, vp, vp, P(i32)]
     L.fc_consensus_cut.argtypes = [vp, c_int, vp, P(i64)]
     L.fc_consensus_levels_timing.argtypes = [vp, P(dbl)]
+    L.fc_coassociation.argtypes = [vp, i64, vp, i64, vp, vp]   # na, a (host), nb, b (host or NULL), dev_out
+    L.fc_coassoc_pairs.argtypes = [vp, i64, vp, vp]            # npairs, pairs (host), dev_out
+    L.fc_coassoc_hist.argtypes = [vp, i64, vp, _i64p]          # k, nodes (host), hist int64[n_r + 1]
+    L.fc_coassoc_timing.argtypes = [vp, P(dbl)]
     _lib = L
     return L
 

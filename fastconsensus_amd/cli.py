@@ -8,14 +8,17 @@ the consensus partition (``Engine.consensus_partition``) to ``consensus_t.../par
 community per line) and ``consensus_t.../membership`` (``node+1<TAB>community+1``, sorted by node).
 ``--consensus-levels`` picks the threshold itself (``Engine.consensus_levels``): the same two
 files hold the level of largest modularity, and ``consensus_t.../levels.tsv`` one row per level.
+``--coassoc K`` writes, beside the output tree, ``coassoc.npy`` (the int32 [K, K] consensus matrix
+of K nodes drawn by ``numpy.random.default_rng(seed)``, ``Engine.coassociation``) and
+``coassoc_nodes.txt`` (their labels, one per line, in the matrix's order).
 """
 import argparse
 import os
 import sys
 
 from ._lib import FC_ALGO_LOUVAIN, FC_ALGO_LOUVAIN_NC
-from .core import (ALGORITHMS, OUT_OF_SCOPE, RULES, Engine, IdGraph, algo_id, best_consensus, labels_to_output,
-                   theta_of)
+from .core import (ALGORITHMS, OUT_OF_SCOPE, RULES, Engine, IdGraph, algo_id, best_consensus, coassoc_nodes,
+                   labels_to_output, theta_of)
 
 DEFAULT_TAU = {'louvain': 0.2, 'cnm': 0.7, 'infomap': 0.6, 'lpm': 0.8}   # :426
 
@@ -56,6 +59,8 @@ def build_parser():
     p.add_argument('--consensus', type=float, default=None, help=argparse.SUPPRESS)
     # extension: the consensus hierarchy; writes every level's record and the best level's partition
     p.add_argument('--consensus-levels', action='store_true', help=argparse.SUPPRESS)
+    # extension: the consensus matrix of K random nodes
+    p.add_argument('--coassoc', type=int, default=None, help=argparse.SUPPRESS)
     return p
 
 
@@ -120,6 +125,16 @@ def write_levels(args, node_labels, levels, labels, root='.'):
                               + [repr(float(r['modularity']))]) + '\n')
 
 
+def write_coassoc(node_labels, ids, matrix, root='.'):
+    """coassoc.npy (int32 [K, K]) and coassoc_nodes.txt (the K node labels, one per line, in the
+    matrix's order), beside the output tree."""
+    import numpy as np
+    np.save(os.path.join(root, 'coassoc.npy'), matrix)
+    with open(os.path.join(root, 'coassoc_nodes.txt'), 'w') as f:
+        for x in node_labels[ids].tolist():
+            f.write(str(x) + '\n')
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.t is None:
@@ -130,8 +145,10 @@ def main(argv=None):
         raise SystemExit("--consensus must lie in [0, 1]")
     if args.consensus is not None and args.consensus_levels:
         raise SystemExit("--consensus and --consensus-levels both write the consensus partition: give one")
-    cons = None
+    cons = ca = None
     g = IdGraph.from_edgelist_file(args.f)
+    if args.coassoc is not None and not 0 <= args.coassoc <= g.n:
+        raise SystemExit("--coassoc must lie in [0, %d], the number of nodes" % g.n)
     algo = algo_id(args.alg)
     if algo is None:
         output = None
@@ -145,6 +162,9 @@ def main(argv=None):
                 cons = eng.consensus_partition(args.consensus)
             if args.consensus_levels:
                 cons = best_consensus(eng)
+            if args.coassoc is not None:
+                ids = coassoc_nodes(g.n, args.coassoc, g.labels, args.seed)
+                ca = (ids, eng.coassociation(ids).cpu().numpy())
         output = labels_to_output(args.alg, g.labels, labels)
     if output is None:                            # reference: TypeError on len(None)
         raise SystemExit("fast_consensus returned None")
@@ -153,6 +173,8 @@ def main(argv=None):
         write_levels(args, g.labels, cons["levels"], cons["labels"])
     elif cons is not None:
         write_consensus(args, g.labels, cons["labels"])
+    if ca is not None:
+        write_coassoc(g.labels, *ca)
 
 
 if __name__ == "__main__":

@@ -450,6 +450,68 @@ class Engine:
         check(self._L.fc_consensus_levels_timing(self._ctx, ms))
         return dict(zip(("bucket", "tree", "statistics", "join_levels"), ms))
 
+    # -- co-association (fc_coassociation / fc_coassoc_pairs / fc_coassoc_hist) -------------
+    @staticmethod
+    def _node_ids(ids, width=None):
+        """ids as a C-contiguous int32 array with at least one element's worth of storage (so
+        its address is never NULL); an id that does not fit int32 becomes -1, which the library
+        rejects with its index."""
+        a = np.asarray(ids)
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("node ids must be integers (positions in node order)")
+        if a.size and a.dtype != np.int32:
+            a = a.astype(np.int64)
+            a = np.where((a < 0) | (a > 2 ** 31 - 1), -1, a)
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        a = a.reshape(-1) if width is None else a.reshape(-1, width)
+        return a if a.size else np.zeros((1,) if width is None else (1, width), np.int32)[:0]
+
+    def _ca_out(self, dev_out, count):
+        import torch
+        if dev_out is None:
+            return torch.empty(max(count, 1), dtype=torch.int32, device="cuda:%d" % self.device)
+        if dev_out.dtype != torch_int32() or dev_out.numel() < count or not dev_out.is_contiguous():
+            raise ValueError("dev_out must be a contiguous int32 tensor of >= %d elements" % count)
+        return dev_out
+
+    def coassociation(self, a, b=None, dev_out=None):
+        """The consensus matrix of two node lists: an int32 device tensor [na, nb] whose entry
+        (i, j) is the number of local labelings that put node a[i] and node b[j] in one community
+        (b=None: b = a).  Node ids are the caller's node order (the columns of get_labels); any
+        order, duplicates allowed.  Written into `dev_out` (int32, >= na * nb elements) when
+        given.  Ranks add theirs (SUM)."""
+        a = self._node_ids(a)
+        b = None if b is None else self._node_ids(b)
+        na, nb = len(a), len(a if b is None else b)
+        out = self._ca_out(dev_out, na * nb)
+        check(self._L.fc_coassociation(self._ctx, na, ptr(a), nb, ptr(b), self._dev(out)))
+        return out.reshape(-1)[:na * nb].view(na, nb)
+
+    def coassoc_pairs(self, pairs, dev_out=None):
+        """Per node pair (pairs[p][0], pairs[p][1]), the number of local labelings that put the
+        two in one community: an int32 device tensor [npairs]."""
+        pairs = self._node_ids(pairs, 2)
+        out = self._ca_out(dev_out, len(pairs))
+        check(self._L.fc_coassoc_pairs(self._ctx, len(pairs), ptr(pairs), self._dev(out)))
+        return out.reshape(-1)[:len(pairs)]
+
+    def coassoc_hist(self, nodes):
+        """int64 [n_r + 1]: hist[s] = the number of unordered position pairs i < j of `nodes`
+        that s local labelings put in one community.  No matrix is formed (k = 65536 is 2.1 G
+        pairs).  pac(hist) and consensus_cdf(hist) read it.  A sharded run's histogram is not the
+        sum of the ranks' histograms: see distributed.coassoc_hist_sharded."""
+        nodes = self._node_ids(nodes)
+        hist = np.zeros(self.replica_info()[0] + 1, np.int64)
+        check(self._L.fc_coassoc_hist(self._ctx, len(nodes), ptr(nodes), hist))
+        return hist
+
+    def coassoc_timing(self):
+        """Device milliseconds of the phases of the last co-association call made with timing on
+        (set_timing): ids (upload and map to internal vertices), count (the kernel)."""
+        ms = (ctypes.c_double * 2)()
+        check(self._L.fc_coassoc_timing(self._ctx, ms))
+        return dict(zip(("ids", "count"), ms))
+
     def nmi_matrix(self):
         """Symmetric [n_r, n_r] float64 NMI between the local replicas (unit diagonal)."""
         return self._pair_matrices()[0]
@@ -514,6 +576,56 @@ def stability(node_in, node_out):
     out = np.ones(len(tot), np.float64)
     nz = tot != 0
     out[nz] = node_in[nz] / tot[nz]
+    return out
+
+
+def pac(hist, lo=0.1, hi=0.9):
+    """Proportion of ambiguous clustering of a co-association histogram (Engine.coassoc_hist):
+    with n = len(hist) - 1, the share of the pairs whose count s has lo * n < s < hi * n (float64
+    comparisons); 0.0 for a histogram without pairs."""
+    hist = np.asarray(hist, np.int64)
+    n = len(hist) - 1
+    total = int(hist.sum())
+    if total == 0:
+        return 0.0
+    s = np.arange(n + 1, dtype=np.float64)
+    mid = (s > np.float64(lo) * np.float64(n)) & (s < np.float64(hi) * np.float64(n))
+    return float(int(hist[mid].sum()) / total)
+
+
+def consensus_cdf(hist):
+    """float64 [n + 1]: the share of the pairs with a count <= s (cumsum(hist) / hist.sum());
+    zeros for a histogram without pairs."""
+    hist = np.asarray(hist, np.int64)
+    total = int(hist.sum())
+    if total == 0:
+        return np.zeros(len(hist), np.float64)
+    return np.cumsum(hist) / total
+
+
+def coassoc_nodes(n, coassoc, labels, seed):
+    """Node ids (positions in node order) of fast_consensus(coassoc=...): an int k draws k of
+    the n nodes without replacement by numpy.random.default_rng(seed); a list holds the
+    caller's node labels."""
+    if isinstance(coassoc, (int, np.integer)) and not isinstance(coassoc, bool):
+        if not 0 <= coassoc <= n:
+            raise ValueError("coassoc=%d: the graph has %d nodes" % (coassoc, n))
+        return np.random.default_rng(seed).choice(n, size=int(coassoc), replace=False).astype(np.int32)
+    index = {x: i for i, x in enumerate(np.asarray(labels).tolist())}
+    try:
+        return np.asarray([index[x] for x in coassoc], np.int32)
+    except KeyError as e:
+        raise ValueError("coassoc: %r is not a node of the graph" % (e.args[0],)) from None
+
+
+def coassoc_result(eng, ids, node_labels, cons=None):
+    """The `coassoc` dict of fast_consensus(coassoc=...) from the engine's local labelings."""
+    node_labels = np.asarray(node_labels)
+    hist = eng.coassoc_hist(ids)
+    out = {"nodes": [node_labels[i] for i in ids.tolist()] if node_labels.dtype == object else node_labels[ids].tolist(),
+           "matrix": eng.coassociation(ids).cpu().numpy(), "hist": hist, "pac": pac(hist), "cdf": consensus_cdf(hist)}
+    if cons is not None:
+        out["order"] = np.argsort(cons["labels"][ids], kind="stable")
     return out
 
 
@@ -851,7 +963,8 @@ def relabel_for(algorithm):
 
 
 def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, seed=None, device=0,
-                   return_stats=False, rule="fast_consensus", scores=False, truth=None, consensus=None):
+                   return_stats=False, rule="fast_consensus", scores=False, truth=None, consensus=None,
+                   coassoc=None):
     """Drop-in for fast_consensus.py:129 ``fast_consensus(G, algorithm, n_p, thresh, delta)``.
 
     G: an undirected networkx Graph (weights are ignored: the reference resets them to 1,
@@ -883,6 +996,14 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     modularity on G (the strictest among equals).  The ``consensus`` dict then also holds
     ``level``, ``theta``, ``levels`` (one record per level), ``birth`` and ``up`` (the tree:
     ``cut_tree(birth, up, s)`` gives any other level).
+
+    ``coassoc=nodes`` (a list of node labels, or an int k: k nodes drawn without replacement by
+    ``numpy.random.default_rng(seed)``) appends a ``coassoc`` dict to the returned tuple, after
+    ``consensus`` when present: ``nodes``, ``matrix`` (numpy int32 [k, k]: how many of the n_p
+    partitions put two of the nodes together), ``hist`` (the counts' histogram over the pairs
+    i < j, ``Engine.coassoc_hist``), ``pac`` and ``cdf`` (``pac(hist)``, ``consensus_cdf(hist)``)
+    and, with ``consensus`` also given, ``order``: the stable argsort of the nodes by consensus
+    label, so that ``matrix[order][:, order]`` is the block heatmap.
     """
     if isinstance(consensus, str) and consensus != "best":
         raise ValueError('consensus must be a threshold in [0, 1] or "best"')
@@ -912,6 +1033,9 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
             cons = best_consensus(eng)
         else:
             cons = eng.consensus_partition(float(consensus)) if consensus is not None else None
+        ca = None
+        if coassoc is not None:   # before consensus_scores replaces the labelings
+            ca = coassoc_result(eng, coassoc_nodes(g.n, coassoc, g.labels, seed), g.labels, cons)
         sc = run_scores(eng, tr) if scores else None
         if cons is not None and scores:
             consensus_scores(eng, sc, cons, tr)
@@ -919,7 +1043,7 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     if cons is not None:
         cons["partition"] = dict(zip(np.asarray(g.labels).tolist(), cons["labels"].tolist()))
     res = (out,) + ((stats,) if return_stats else ()) + ((sc,) if scores else ()) + \
-        ((cons,) if cons is not None else ())
+        ((cons,) if cons is not None else ()) + ((ca,) if ca is not None else ())
     return res if len(res) > 1 else out
 
 

@@ -157,7 +157,8 @@ void fc_destroy(fc_ctx* ctx) {
                       &c.st_lab, &c.clo_rec, &c.clo_hkey, &c.clo_hval, &c.clo_list, &c.clo_cnt, &c.clo_akey, &c.clo_aval, &c.clo_rowptr, &c.clo_col, &c.clo_rowptr2, &c.clo_col2, &c.clo_nrow, &c.clo_ncol, &c.clo_own, &c.clo_own2, &c.mvf,
                       &c.sc_ref, &c.sc_key, &c.sc_val, &c.sc_ulab, &c.sc_cnt, &c.sc_nruns, &c.sc_seg, &c.sc_kd, &c.sc_kp, &c.sc_part, &c.sc_part2, &c.sc_res, &c.sc_want, &c.sc_ovf, &c.sc_e1, &c.sc_e2, &c.sc_fk1, &c.sc_fk2, &c.sc_fcnt, &c.sc_rng,
                       &c.cp_sup, &c.cp_parent, &c.cp_flag, &c.cp_rank, &c.cp_lab, &c.cp_labi, &c.cp_size, &c.cp_hist, &c.cp_nin, &c.cp_nout,
-                      &c.lv_birth, &c.lv_up, &c.lv_cursor, &c.lv_bucket, &c.lv_tot, &c.lv_stats, &c.lv_fold, &c.lv_jw};
+                      &c.lv_birth, &c.lv_up, &c.lv_cursor, &c.lv_bucket, &c.lv_tot, &c.lv_stats, &c.lv_fold, &c.lv_jw,
+                      &c.ca_ids, &c.ca_va, &c.ca_vb, &c.ca_hist};
     for (auto* b : bufs) b->release();
     for (auto e : c.timer.pool) (void)hipEventDestroy(e);
     for (auto e : c.sweep_ev) (void)hipEventDestroy(e);
@@ -566,6 +567,62 @@ int fc_consensus_levels_timing(fc_ctx* ctx, double* ms) {
     FC_API_BEGIN
     FC_REQUIRE(ms, FC_EINVAL, "null output buffer");
     for (int i = 0; i < LV_PHASES; ++i) ms[i] = c.lv_ms[i];
+    FC_API_END
+}
+
+// co-association: the state checks of score_require come first, then every node id on the host
+static void coassoc_state(const Ctx& c) {
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings: run fc_run, fc_cd or fc_set_labels first");
+}
+static void coassoc_ids(const Ctx& c, const char* what, const int32_t* ids, int64_t count) {
+    FC_REQUIRE(count >= 0, FC_EINVAL, std::string("negative length of ") + what);
+    FC_REQUIRE(ids || count == 0, FC_EINVAL, std::string("null ") + what);
+    const uint32_t lim = (uint32_t)c.N;
+    for (int64_t i = 0; i < count; ++i)
+        FC_REQUIRE((uint32_t)ids[i] < lim, FC_EINVAL,
+                   std::string(what) + ": node " + std::to_string(ids[i]) + " at index " + std::to_string(i) +
+                       " outside [0, n)");
+}
+
+int fc_coassociation(fc_ctx* ctx, int64_t na, const int32_t* a, int64_t nb, const int32_t* b, void* dev_out) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    coassoc_state(c);
+    coassoc_ids(c, "a", a, na);
+    if (b) coassoc_ids(c, "b", b, nb);
+    const int64_t cols = b ? nb : na;
+    FC_REQUIRE(dev_out || na == 0 || cols == 0, FC_EINVAL, "null output buffer");
+    coassoc_matrix(c, na, a, nb, b, (int32_t*)dev_out);
+    FC_API_END
+}
+
+int fc_coassoc_pairs(fc_ctx* ctx, int64_t npairs, const int32_t* pairs, void* dev_out) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    coassoc_state(c);
+    FC_REQUIRE(npairs >= 0 && npairs < ((int64_t)1 << 40), FC_EINVAL, "bad pair count");
+    coassoc_ids(c, "pairs", pairs, 2 * npairs);
+    FC_REQUIRE(dev_out || npairs == 0, FC_EINVAL, "null output buffer");
+    coassoc_pairs(c, npairs, pairs, (int32_t*)dev_out);
+    FC_API_END
+}
+
+int fc_coassoc_hist(fc_ctx* ctx, int64_t k, const int32_t* nodes, int64_t* hist) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    coassoc_state(c);
+    coassoc_ids(c, "nodes", nodes, k);
+    FC_REQUIRE(hist, FC_EINVAL, "null output buffer");
+    coassoc_hist(c, k, nodes, hist);
+    FC_API_END
+}
+
+int fc_coassoc_timing(fc_ctx* ctx, double* ms) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(ms, FC_EINVAL, "null output buffer");
+    for (int i = 0; i < CA_PHASES; ++i) ms[i] = c.ca_ms[i];
     FC_API_END
 }
 

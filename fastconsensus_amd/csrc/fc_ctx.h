@@ -254,6 +254,11 @@ struct Ctx {
     DevBuf lv_birth, lv_up, lv_cursor, lv_bucket, lv_tot, lv_stats, lv_fold, lv_jw;
     bool lv_valid = false;
     int lv_nt = 0;
+    // co-association (coassoc.h): the caller's node ids as uploaded, the two lists as internal
+    // vertices, the count histogram
+    // device time of the last call's phases (timing enabled): ids (upload + map), count
+    double ca_ms[2] = {0, 0};
+    DevBuf ca_ids, ca_va, ca_vb, ca_hist;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = getenv("FC_SCORE_SLOW") ? atoi(getenv("FC_SCORE_SLOW")) : 0;
     // longest community one wave streams; longer ones go to the fallback
@@ -265,6 +270,7 @@ struct Ctx {
 struct Ctx;
 constexpr int CP_PHASES = 5;        // Ctx::cp_ms
 constexpr int LV_PHASES = 4;        // Ctx::lv_ms
+constexpr int CA_PHASES = 2;        // Ctx::ca_ms
 constexpr int FC_HPIN_I64 = 2048;   // pinned host scratch: per-sweep records (cd_rl.hip: boff | voff | n_active)
 // State the replica-lane engine hands to cd_run at the first filtered sweep of a hybrid batch
 // (FC_OPT_CD_ENGINE=2, cd_rl.hip): fill() writes it in cd.hip's layout on c.stream -- labels
@@ -385,6 +391,10 @@ void consensus_partition(Ctx& c, int graph, const int32_t* dev_support, int n_to
 void consensus_levels(Ctx& c, int graph, const int32_t* dev_support, int n_total, int32_t* birth_out, int32_t* up_out,
                       fc_level_score* levels_out, int32_t* best_out);
 void consensus_cut(Ctx& c, int level, int32_t* labels_out, int64_t* k_out);
+// coassoc.h (in consensus.hip): node ids on the host, validated by the caller; b null: b = a
+void coassoc_matrix(Ctx& c, int64_t na, const int32_t* a, int64_t nb, const int32_t* b, int32_t* dev_out);
+void coassoc_pairs(Ctx& c, int64_t npairs, const int32_t* pairs, int32_t* dev_out);
+void coassoc_hist(Ctx& c, int64_t k, const int32_t* nodes, int64_t* hist);
 // timing helpers
 int timer_begin(Ctx& c);
 void timer_end(Ctx& c, int slot, int begin_ev);

@@ -155,6 +155,38 @@ def _consensus(engine, theta, n_p, world, mine, device):
     return engine.consensus_partition(theta, "input", dev_support=sup, n_total=n_p)
 
 
+def coassociation_sharded(engine, a, b=None, device="cuda"):
+    """The consensus matrix of two node lists (Engine.coassociation) over every rank's replicas:
+    each rank counts over ITS local labelings, one int32 SUM all-reduce adds the counts, and every
+    rank returns the same int32 [na, nb] tensor on `device`.  A rank without replicas
+    contributes zeros."""
+    na = len(np.asarray(a).reshape(-1))
+    nb = na if b is None else len(np.asarray(b).reshape(-1))
+    if engine.replica_info()[0] > 0:
+        mat = engine.coassociation(a, b)
+        if not str(device).startswith("cuda"):
+            mat = mat.cpu()
+    else:
+        mat = torch.zeros((na, nb), dtype=torch.int32, device=device)
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        mat = mat.contiguous()
+        dist.all_reduce(mat, op=dist.ReduceOp.SUM)
+    return mat
+
+
+def coassoc_hist_sharded(engine, nodes, n_total, device="cuda"):
+    """int64 [n_total + 1] histogram of the counts over the position pairs i < j of `nodes`,
+    over all n_total replicas of a sharded run.  A histogram of sums is not a sum of histograms
+    -- a pair's count is spread over the ranks, and which bin it falls in is known only after the
+    counts are added -- so Engine.coassoc_hist (fc_coassoc_hist) does not shard: this takes the
+    reduced matrix of coassociation_sharded and bins its strict upper triangle with
+    torch.bincount.  The matrix limits it to lists whose k * k counts fit in memory."""
+    mat = coassociation_sharded(engine, nodes, None, device)
+    k = mat.shape[0]
+    iu = torch.triu_indices(k, k, offset=1, device=mat.device)
+    return torch.bincount(mat[iu[0], iu[1]].to(torch.int64), minlength=int(n_total) + 1).cpu().numpy()
+
+
 def _result(res, consensus):
     labels, st = res
     return (labels, st) if consensus is None else (labels, st, st.pop("consensus"))

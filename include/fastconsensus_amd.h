@@ -382,6 +382,27 @@ int fc_consensus_cut(fc_ctx* ctx, int level, int32_t* labels_out, int64_t* k_out
  * nonempty level), statistics (fold of the per-level counters), join levels. */
 int fc_consensus_levels_timing(fc_ctx* ctx, double* ms);
 
+/* ---- co-association: how many local labelings put two nodes together ------------------- */
+/* Node ids are the caller's node order (the columns of fc_get_labels), duplicates and any order
+ * allowed; the lists are host arrays.  Every call reads labels only (graph, labelings and random
+ * state are afterwards what they were), works on the context's stream and returns after it has
+ * finished.  FC_ESTATE: no graph or no labelings; FC_EINVAL: a node id outside [0, n) (the message
+ * names the index), checked before anything is launched; FC_ELIMIT: more than 2048 local
+ * replicas.  A length of 0 is legal and launches nothing.  Reduce the counts with SUM across
+ * ranks. */
+/* out[i*nb + j] = #local replicas that put node a[i] and node b[j] together; b == NULL: b = a.
+   a, b: host int32 node ids in [0, n); dev_out: device int32[na*nb]. */
+int fc_coassociation(fc_ctx* ctx, int64_t na, const int32_t* a, int64_t nb, const int32_t* b, void* dev_out);
+/* counts[p] for node pairs (pairs[2p], pairs[2p+1]); dev_out: device int32[npairs] */
+int fc_coassoc_pairs(fc_ctx* ctx, int64_t npairs, const int32_t* pairs, void* dev_out);
+/* hist[s], s = 0..n_r, over the unordered position pairs i < j of the list; host int64[n_r + 1]
+ * (n_r: the local replica count of fc_replica_info).  No matrix is formed: k = 65536 is 2.1 G
+ * pairs.  The histogram of a sharded run is not the sum of the ranks' histograms. */
+int fc_coassoc_hist(fc_ctx* ctx, int64_t k, const int32_t* nodes, int64_t* hist);
+/* Device time (ms, HIP events) of the phases of the last co-association call made with timing
+ * enabled: ms[2] = ids (upload and map to internal vertices), count (the kernel). */
+int fc_coassoc_timing(fc_ctx* ctx, double* ms);   /* phases of the last call, timing enabled only */
+
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
  * Writes at most m_cap edges into u/v and the planted community of every node. */
