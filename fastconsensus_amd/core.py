@@ -368,17 +368,31 @@ class Engine:
             raise ValueError("dev_support must be an int32 tensor of >= %d elements" % m)
         return int(n_total)
 
+    def _phase_timing(self, fn, names):
+        """{name: device milliseconds} of the phases one fc_*_timing getter reports."""
+        ms = (ctypes.c_double * len(names))()
+        check(fn(self._ctx, ms))
+        return dict(zip(names, ms))
+
+    def _int32_out(self, dev_out, count, contiguous=False):
+        """An int32 device tensor of at least `count` elements: `dev_out` when given (checked), else
+        a new one."""
+        import torch
+        if dev_out is None:
+            return torch.empty(max(count, 1), dtype=torch.int32, device="cuda:%d" % self.device)
+        if dev_out.dtype != torch_int32() or dev_out.numel() < count or \
+                (contiguous and not dev_out.is_contiguous()):
+            raise ValueError("dev_out must be %s int32 tensor of >= %d elements"
+                             % ("a contiguous" if contiguous else "an", count))
+        return dev_out
+
     def consensus_support(self, graph="input", dev_out=None):
         """Per edge of `graph`, the number of local labelings that put both ends in one community:
         an int32 device tensor [m] in the engine's edge order (consensus_partial's; the same on
         every engine that loaded the graph with the same seed and options), written into
         `dev_out` when given.  Ranks add theirs (SUM) and hand the total to consensus_partition."""
-        import torch
         m = self._graph_edges(graph)
-        if dev_out is None:
-            dev_out = torch.empty(max(m, 1), dtype=torch.int32, device="cuda:%d" % self.device)
-        elif dev_out.dtype != torch_int32() or dev_out.numel() < m:
-            raise ValueError("dev_out must be an int32 tensor of >= %d elements" % m)
+        dev_out = self._int32_out(dev_out, m)
         check(self._L.fc_consensus_support(self._ctx, _lib.SCORE_GRAPHS[graph], self._dev(dev_out)))
         self._written()
         return dev_out[:m]
@@ -411,9 +425,8 @@ class Engine:
     def consensus_timing(self):
         """Device milliseconds of the phases of the last consensus_partition made with timing on
         (set_timing): support, histogram, components, renumber (+ sizes), node_sums."""
-        ms = (ctypes.c_double * 5)()
-        check(self._L.fc_consensus_timing(self._ctx, ms))
-        return dict(zip(("support", "histogram", "components", "renumber", "node_sums"), ms))
+        return self._phase_timing(self._L.fc_consensus_timing,
+                                  ("support", "histogram", "components", "renumber", "node_sums"))
 
     # -- the consensus hierarchy (fc_consensus_levels / fc_consensus_cut) ------------------
     def consensus_levels(self, graph="input", dev_support=None, n_total=None):
@@ -446,9 +459,8 @@ class Engine:
     def consensus_levels_timing(self):
         """Device milliseconds of the phases of the last consensus_levels made with timing on
         (set_timing): bucket, tree, statistics, join_levels."""
-        ms = (ctypes.c_double * 4)()
-        check(self._L.fc_consensus_levels_timing(self._ctx, ms))
-        return dict(zip(("bucket", "tree", "statistics", "join_levels"), ms))
+        return self._phase_timing(self._L.fc_consensus_levels_timing,
+                                  ("bucket", "tree", "statistics", "join_levels"))
 
     # -- co-association (fc_coassociation / fc_coassoc_pairs / fc_coassoc_hist) -------------
     @staticmethod
@@ -466,14 +478,6 @@ class Engine:
         a = a.reshape(-1) if width is None else a.reshape(-1, width)
         return a if a.size else np.zeros((1,) if width is None else (1, width), np.int32)[:0]
 
-    def _ca_out(self, dev_out, count):
-        import torch
-        if dev_out is None:
-            return torch.empty(max(count, 1), dtype=torch.int32, device="cuda:%d" % self.device)
-        if dev_out.dtype != torch_int32() or dev_out.numel() < count or not dev_out.is_contiguous():
-            raise ValueError("dev_out must be a contiguous int32 tensor of >= %d elements" % count)
-        return dev_out
-
     def coassociation(self, a, b=None, dev_out=None):
         """The consensus matrix of two node lists: an int32 device tensor [na, nb] whose entry
         (i, j) is the number of local labelings that put node a[i] and node b[j] in one community
@@ -483,7 +487,7 @@ class Engine:
         a = self._node_ids(a)
         b = None if b is None else self._node_ids(b)
         na, nb = len(a), len(a if b is None else b)
-        out = self._ca_out(dev_out, na * nb)
+        out = self._int32_out(dev_out, na * nb, contiguous=True)
         check(self._L.fc_coassociation(self._ctx, na, ptr(a), nb, ptr(b), self._dev(out)))
         return out.reshape(-1)[:na * nb].view(na, nb)
 
@@ -491,7 +495,7 @@ class Engine:
         """Per node pair (pairs[p][0], pairs[p][1]), the number of local labelings that put the
         two in one community: an int32 device tensor [npairs]."""
         pairs = self._node_ids(pairs, 2)
-        out = self._ca_out(dev_out, len(pairs))
+        out = self._int32_out(dev_out, len(pairs), contiguous=True)
         check(self._L.fc_coassoc_pairs(self._ctx, len(pairs), ptr(pairs), self._dev(out)))
         return out.reshape(-1)[:len(pairs)]
 
@@ -508,9 +512,7 @@ class Engine:
     def coassoc_timing(self):
         """Device milliseconds of the phases of the last co-association call made with timing on
         (set_timing): ids (upload and map to internal vertices), count (the kernel)."""
-        ms = (ctypes.c_double * 2)()
-        check(self._L.fc_coassoc_timing(self._ctx, ms))
-        return dict(zip(("ids", "count"), ms))
+        return self._phase_timing(self._L.fc_coassoc_timing, ("ids", "count"))
 
     def nmi_matrix(self):
         """Symmetric [n_r, n_r] float64 NMI between the local replicas (unit diagonal)."""

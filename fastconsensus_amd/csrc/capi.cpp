@@ -103,6 +103,15 @@ struct fc_ctx {
     Ctx& c = (ctx)->c;                                           \
     bind(c);
 
+// the fc_*_timing getters: the device time of the last call's phases (Ctx::cp_ms / lv_ms / ca_ms)
+template <int N> static int phase_timing(fc_ctx* ctx, double (Ctx::*src)[N], double* ms) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(ms, FC_EINVAL, "null output buffer");
+    for (int i = 0; i < N; ++i) ms[i] = (c.*src)[i];
+    FC_API_END
+}
+
 extern "C" {
 
 const char* fc_last_error(void) { return g_err.c_str(); }
@@ -457,13 +466,22 @@ int fc_score_set_reference(fc_ctx* ctx, const int32_t* labels) {
     FC_API_END
 }
 
+static bool score_graph_id(int graph) { return graph == FC_SCORE_GRAPH_INPUT || graph == FC_SCORE_GRAPH_WORKING; }
+// what fc_consensus_partition and fc_consensus_levels require of the graph id, the support and the state
+static void consensus_input(const Ctx& c, int graph, const void* dev_support, int n_total) {
+    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    FC_REQUIRE(!dev_support || n_total >= 1, FC_EINVAL, "reduced support needs n_total >= 1");
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(dev_support || c.n_r > 0, FC_ESTATE,
+               "no labelings and no support: run fc_run, fc_cd or fc_set_labels first, or pass dev_support");
+}
+
 int fc_score_partitions(fc_ctx* ctx, int graph, fc_part_score* out) {
     FC_CTX(ctx)
     FC_API_BEGIN
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
     FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings");
-    FC_REQUIRE(graph == FC_SCORE_GRAPH_INPUT || graph == FC_SCORE_GRAPH_WORKING, FC_EINVAL,
-               "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
     FC_REQUIRE(out, FC_EINVAL, "null output buffer");
     score_partitions(c, graph, out);
     FC_API_END
@@ -502,8 +520,6 @@ int fc_score_pairs(fc_ctx* ctx, const int32_t* pairs, int64_t* npairs, fc_pair_s
     FC_API_END
 }
 
-static bool score_graph_id(int graph) { return graph == FC_SCORE_GRAPH_INPUT || graph == FC_SCORE_GRAPH_WORKING; }
-
 int fc_consensus_support(fc_ctx* ctx, int graph, void* dev_out) {
     FC_CTX(ctx)
     FC_API_BEGIN
@@ -521,33 +537,19 @@ int fc_consensus_partition(fc_ctx* ctx, int graph, const void* dev_support, int 
     FC_CTX(ctx)
     FC_API_BEGIN
     FC_REQUIRE(agreement >= 0.0 && agreement <= 1.0, FC_EINVAL, "agreement must lie in [0, 1]");   // NaN fails both
-    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
-    FC_REQUIRE(!dev_support || n_total >= 1, FC_EINVAL, "reduced support needs n_total >= 1");
-    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
-    FC_REQUIRE(dev_support || c.n_r > 0, FC_ESTATE,
-               "no labelings and no support: run fc_run, fc_cd or fc_set_labels first, or pass dev_support");
+    consensus_input(c, graph, dev_support, n_total);
     consensus_partition(c, graph, (const int32_t*)dev_support, n_total, agreement, labels_out, support_hist, node_in,
                         node_out, info);
     FC_API_END
 }
 
-int fc_consensus_timing(fc_ctx* ctx, double* ms) {
-    FC_CTX(ctx)
-    FC_API_BEGIN
-    FC_REQUIRE(ms, FC_EINVAL, "null output buffer");
-    for (int i = 0; i < CP_PHASES; ++i) ms[i] = c.cp_ms[i];
-    FC_API_END
-}
+int fc_consensus_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::cp_ms, ms); }
 
 int fc_consensus_levels(fc_ctx* ctx, int graph, const void* dev_support, int n_total, int32_t* birth, int32_t* up,
                         fc_level_score* levels, int32_t* best_level) {
     FC_CTX(ctx)
     FC_API_BEGIN
-    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
-    FC_REQUIRE(!dev_support || n_total >= 1, FC_EINVAL, "reduced support needs n_total >= 1");
-    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
-    FC_REQUIRE(dev_support || c.n_r > 0, FC_ESTATE,
-               "no labelings and no support: run fc_run, fc_cd or fc_set_labels first, or pass dev_support");
+    consensus_input(c, graph, dev_support, n_total);
     consensus_levels(c, graph, (const int32_t*)dev_support, n_total, birth, up, levels, best_level);
     FC_API_END
 }
@@ -562,13 +564,7 @@ int fc_consensus_cut(fc_ctx* ctx, int level, int32_t* labels_out, int64_t* k_out
     FC_API_END
 }
 
-int fc_consensus_levels_timing(fc_ctx* ctx, double* ms) {
-    FC_CTX(ctx)
-    FC_API_BEGIN
-    FC_REQUIRE(ms, FC_EINVAL, "null output buffer");
-    for (int i = 0; i < LV_PHASES; ++i) ms[i] = c.lv_ms[i];
-    FC_API_END
-}
+int fc_consensus_levels_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::lv_ms, ms); }
 
 // co-association: the state checks of score_require come first, then every node id on the host
 static void coassoc_state(const Ctx& c) {
@@ -618,13 +614,7 @@ int fc_coassoc_hist(fc_ctx* ctx, int64_t k, const int32_t* nodes, int64_t* hist)
     FC_API_END
 }
 
-int fc_coassoc_timing(fc_ctx* ctx, double* ms) {
-    FC_CTX(ctx)
-    FC_API_BEGIN
-    FC_REQUIRE(ms, FC_EINVAL, "null output buffer");
-    for (int i = 0; i < CA_PHASES; ++i) ms[i] = c.ca_ms[i];
-    FC_API_END
-}
+int fc_coassoc_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::ca_ms, ms); }
 
 int fc_collect_timing(fc_ctx* ctx, fc_stats* st) {
     FC_CTX(ctx)

@@ -3,8 +3,8 @@
 // The consensus matrix of two node lists, the counts of arbitrary node pairs, and the
 // distribution of the counts over the pairs of one list (what PAC and the consensus CDF need)
 // without the matrix.
-// Included at the end of consensus.hip after levels.h (ScLabT, score_require, launch_pair_partial
-// and ensure are in scope).
+// Included at the end of consensus.hip after levels.h (ScLabT, score_require, launch_pair_partial,
+// ensure and the helpers of analysis.h are in scope).
 //
 // Tile core: a 256-thread block owns 64 x 64 pairs.  Per bank of 64 replicas it stages the 64 + 64
 // label rows of labT in LDS -- a row is 256 bytes, read by 16 lanes as one int4 each -- and every
@@ -167,37 +167,12 @@ __global__ __launch_bounds__(256) void k_ca_hist(const int32_t* __restrict__ lab
             const int bin = in ? acc[a][b] : -1;
             const unsigned long long act = __ballot(in);
             if (!act) continue;
-            const int src = __ffsll((long long)act) - 1;
-            const int lead = __shfl(bin, src);
-            const unsigned long long same = __ballot(in && bin == lead);
-            if (lane == src) atomicAdd(&s_ca_h[lead], (unsigned int)__popcll(same));
-            if (in && bin != lead) atomicAdd(&s_ca_h[bin], 1u);
+            wave_bin_add(s_ca_h, in, bin, act, lane);
         }
     __syncthreads();
     for (int i = threadIdx.x; i <= n_r; i += blockDim.x)
         if (s_ca_h[i]) atomicAdd(&hist[i], (unsigned long long)s_ca_h[i]);
 }
-
-// phase boundaries of one call as events of the timing pool (timing enabled only)
-namespace {
-struct CaMarks {
-    Ctx& c;
-    int ev[CA_PHASES + 1];
-    int n = 0;
-    explicit CaMarks(Ctx& x) : c(x) {}
-    void mark() {
-        if (c.timer.on && n <= CA_PHASES) ev[n++] = timer_begin(c);
-    }
-    void collect() {   // after a stream synchronise
-        for (int i = 0; i < CA_PHASES; ++i) c.ca_ms[i] = 0.0;
-        for (int i = 0; i + 1 < n; ++i) {
-            float x = 0.f;
-            FC_HIP(hipEventElapsedTime(&x, c.timer.pool[ev[i]], c.timer.pool[ev[i + 1]]));
-            c.ca_ms[i] = x;
-        }
-    }
-};
-}  // namespace
 
 // host node ids (validated by the caller), every stride-th from `first` -> internal vertices in dst
 static int32_t* ca_vertices(Ctx& c, DevBuf& stage, DevBuf& dst, const int32_t* host, int64_t count, int stride,
@@ -214,12 +189,12 @@ static int32_t* ca_vertices(Ctx& c, DevBuf& stage, DevBuf& dst, const int32_t* h
 void coassoc_matrix(Ctx& c, int64_t na, const int32_t* a, int64_t nb, const int32_t* b, int32_t* dev_out) {
     score_require(c);
     if (!b) nb = na;
-    for (int i = 0; i < CA_PHASES; ++i) c.ca_ms[i] = 0.0;
+    PhaseMarks ph(c, c.ca_ms);
+    ph.clear();   // an early return reports all-zero phases
     if (na <= 0 || nb <= 0) return;
     const int64_t tna = (na + CA_T - 1) / CA_T, tnb = (nb + CA_T - 1) / CA_T;
     FC_REQUIRE(tna * tnb < ((int64_t)1 << 31), FC_ELIMIT, "co-association matrix of more than 2^31 tiles");
     ScLabT lt(c);
-    CaMarks ph(c);
     ph.mark();
     const int32_t* va = ca_vertices(c, c.ca_ids, c.ca_va, a, na, 1, 0);
     const int32_t* vb = b ? ca_vertices(c, c.ca_ids, c.ca_vb, b, nb, 1, 0) : va;
@@ -239,10 +214,10 @@ void coassoc_matrix(Ctx& c, int64_t na, const int32_t* a, int64_t nb, const int3
 // consensus_partial on arbitrary vertex pairs.  Synchronises.
 void coassoc_pairs(Ctx& c, int64_t npairs, const int32_t* pairs, int32_t* dev_out) {
     score_require(c);
-    for (int i = 0; i < CA_PHASES; ++i) c.ca_ms[i] = 0.0;
+    PhaseMarks ph(c, c.ca_ms);
+    ph.clear();   // an early return reports all-zero phases
     if (npairs <= 0) return;
     ScLabT lt(c);
-    CaMarks ph(c);
     ph.mark();
     const int32_t* u = ca_vertices(c, c.ca_ids, c.ca_va, pairs, npairs, 2, 0);
     const int32_t* v = ca_vertices(c, c.ca_ids, c.ca_vb, pairs, npairs, 2, 1);
@@ -257,13 +232,13 @@ void coassoc_pairs(Ctx& c, int64_t npairs, const int32_t* pairs, int32_t* dev_ou
 void coassoc_hist(Ctx& c, int64_t k, const int32_t* nodes, int64_t* hist) {
     score_require(c);
     const int n_r = c.n_r;
-    for (int i = 0; i < CA_PHASES; ++i) c.ca_ms[i] = 0.0;
+    PhaseMarks ph(c, c.ca_ms);
+    ph.clear();   // an early return reports all-zero phases
     std::memset(hist, 0, sizeof(int64_t) * ((size_t)n_r + 1));
     if (k < 2) return;
     const int64_t T = (k + CA_T - 1) / CA_T;
     FC_REQUIRE(T * (T + 1) / 2 < ((int64_t)1 << 31), FC_ELIMIT, "co-association histogram of more than 2^31 tiles");
     ScLabT lt(c);
-    CaMarks ph(c);
     ph.mark();
     const int32_t* va = ca_vertices(c, c.ca_ids, c.ca_va, nodes, k, 1, 0);
     unsigned long long* dh = (unsigned long long*)ensure<uint64_t>(c.ca_hist, (size_t)n_r + 1);

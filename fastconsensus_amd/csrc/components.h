@@ -1,8 +1,8 @@
 // components.h -- the consensus partition (fc_consensus_support / fc_consensus_partition): the
 // connected components of the agreement graph, i.e. of the edges of G (or of the working graph)
 // whose endpoints at least `agreement * n_total` labelings put in one community.
-// Included at the end of consensus.hip after score.h (launch_pair_partial, the hipcub wrappers
-// and ScLabT are in scope).
+// Included at the end of consensus.hip after score.h (launch_pair_partial, the hipcub wrappers,
+// ScLabT and the helpers of analysis.h are in scope).
 //
 // Components: a lock-free union-find over NODE ids (npos[internal vertex]).  Every vertex starts
 // as its own parent; one thread per kept edge finds both roots with path halving and hooks the
@@ -38,6 +38,20 @@ __device__ __forceinline__ int32_t cp_find(int32_t* parent, int32_t x) {
     }
     return x;
 }
+// union the trees of a and b: find both roots, hook the larger under the smaller, and after a lost
+// swap go on from the value it returned (the invariants are at the top of this file)
+__device__ __forceinline__ void uf_hook(int32_t* parent, int32_t a, int32_t b) {
+    for (;;) {
+        a = cp_find(parent, a);
+        b = cp_find(parent, b);
+        if (a == b) break;
+        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        const int32_t old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) break;
+        a = old;   // hi was hooked meanwhile: go on from its new parent
+        b = lo;
+    }
+}
 
 __global__ void k_cp_init(int64_t N, int32_t* parent) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -50,17 +64,7 @@ __global__ __launch_bounds__(256) void k_cp_hook(int64_t m, const int32_t* __res
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= m) return;
     if ((double)sup[e] < cut) return;
-    int32_t a = npos[eu[e]], b = npos[ev[e]];
-    for (;;) {
-        a = cp_find(parent, a);
-        b = cp_find(parent, b);
-        if (a == b) break;
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const int32_t old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) break;
-        a = old;   // hi was hooked meanwhile: go on from its new parent
-        b = lo;
-    }
+    uf_hook(parent, npos[eu[e]], npos[ev[e]]);
 }
 // parent[t] <- root of t; flag[t] = t is a root (flag[N] = 0 closes the scan)
 __global__ void k_cp_flatten(int64_t N, int32_t* parent, int32_t* __restrict__ flag) {
@@ -129,18 +133,10 @@ __global__ __launch_bounds__(256) void k_cp_hist(int64_t m, const int32_t* __res
     for (int64_t e0 = (int64_t)blockIdx.x * blockDim.x; e0 < m; e0 += stride) {   // block-uniform trip count
         const int64_t e = e0 + threadIdx.x;
         const bool in = e < m;
-        int bin = -1;
-        if (in) {
-            const int32_t s = sup[e];
-            bin = (uint32_t)s <= (uint32_t)nt ? s : nt + 1;
-        }
+        const int bin = in ? support_bin(sup[e], nt) : -1;
         const unsigned long long act = __ballot(in);
         if (!act) continue;
-        const int src = __ffsll((long long)act) - 1;
-        const int lead = __shfl(bin, src);
-        const unsigned long long same = __ballot(in && bin == lead);
-        if (lane == src) atomicAdd(&s_cp_h[lead], (unsigned int)__popcll(same));
-        if (in && bin != lead) atomicAdd(&s_cp_h[bin], 1u);
+        wave_bin_add(s_cp_h, in, bin, act, lane);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < nt + 2; i += blockDim.x)
@@ -177,27 +173,6 @@ __global__ __launch_bounds__(256) void k_cp_node_sums(int64_t N, const int64_t* 
     }
 }
 
-// phase boundaries of one call as events of the timing pool (timing enabled only)
-namespace {
-struct CpMarks {
-    Ctx& c;
-    int ev[CP_PHASES + 1];
-    int n = 0;
-    explicit CpMarks(Ctx& x) : c(x) {}
-    void mark() {
-        if (c.timer.on && n <= CP_PHASES) ev[n++] = timer_begin(c);
-    }
-    void collect() {   // after a stream synchronise
-        for (int i = 0; i < CP_PHASES; ++i) c.cp_ms[i] = 0.0;
-        for (int i = 0; i + 1 < n; ++i) {
-            float x = 0.f;
-            FC_HIP(hipEventElapsedTime(&x, c.timer.pool[ev[i]], c.timer.pool[ev[i + 1]]));
-            c.cp_ms[i] = x;
-        }
-    }
-};
-}  // namespace
-
 static const Graph& cp_graph(Ctx& c, int graph) { return graph == FC_SCORE_GRAPH_INPUT ? c.g0 : c.g; }
 
 // support of every edge of the chosen graph over the local labelings (the count kernel of
@@ -211,29 +186,46 @@ void consensus_support(Ctx& c, int graph, int32_t* out) {
     timer_end(c, 1, sl);
 }
 
-// dev_support: null (counted here over the local labelings, n_total = n_r) or int32[m] reduced over
-// n_total replicas.  Outputs (any may be null) are written only when everything succeeded.
-void consensus_partition(Ctx& c, int graph, const int32_t* dev_support, int n_total, double agreement,
-                         int32_t* labels_out, int64_t* hist_out, int64_t* nin_out, int64_t* nout_out,
-                         fc_consensus_info* info) {
+// The opening of consensus_partition and consensus_levels.  dev_support: null (counted here over the
+// local labelings into cp_sup, n_total = n_r) or int32[m] reduced over n_total replicas; `what`
+// names the caller in the replica-limit message.  Opens the call's consensus span and, when
+// `first` is given, marks it before the count: the partition times the count as its first phase.
+struct CpInput {
+    const int32_t* sup;   // device, int32[m]
+    int n_total;
+    int span;             // timer_begin of the call
+};
+static CpInput cp_open(Ctx& c, const Graph& g, const int32_t* dev_support, int n_total, const char* what,
+                       PhaseMarks* first = nullptr) {
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
-    const Graph& g = cp_graph(c, graph);
-    const int64_t N = c.N, m = g.m;
-    const int32_t* sup = dev_support;
-    if (!sup) {
+    if (!dev_support) {
         score_require(c);
         n_total = c.n_r;
     }
-    FC_REQUIRE(n_total <= CP_MAX_TOTAL, FC_ELIMIT, "the consensus partition handles at most 2048 replicas");
-    const int sl = timer_begin(c);
-    CpMarks ph(c);
-    ph.mark();
-    if (!sup) {
-        int32_t* s = ensure<int32_t>(c.cp_sup, m + 1);
+    FC_REQUIRE(n_total <= CP_MAX_TOTAL, FC_ELIMIT,
+               std::string("the consensus ") + what + " handles at most 2048 replicas");
+    CpInput in{dev_support, n_total, timer_begin(c)};
+    if (first) first->mark();
+    if (!in.sup) {
+        int32_t* s = ensure<int32_t>(c.cp_sup, g.m + 1);
         ScLabT lt(c);
-        launch_pair_partial<false>(c, m, g.eu.as<int32_t>(), g.ev.as<int32_t>(), s);
-        sup = s;
+        launch_pair_partial<false>(c, g.m, g.eu.as<int32_t>(), g.ev.as<int32_t>(), s);
+        in.sup = s;
     }
+    return in;
+}
+
+// dev_support as in cp_open.  Outputs (any may be null) are written only when everything succeeded.
+void consensus_partition(Ctx& c, int graph, const int32_t* dev_support, int n_total, double agreement,
+                         int32_t* labels_out, int64_t* hist_out, int64_t* nin_out, int64_t* nout_out,
+                         fc_consensus_info* info) {
+    const Graph& g = cp_graph(c, graph);
+    const int64_t N = c.N, m = g.m;
+    PhaseMarks ph(c, c.cp_ms);
+    const CpInput in = cp_open(c, g, dev_support, n_total, "partition", &ph);
+    const int32_t* sup = in.sup;
+    n_total = in.n_total;
+    const int sl = in.span;
     ph.mark();   // support
     const double cut = agreement * (double)n_total;   // float64 product, compared as in k_consensus_apply
     const int32_t* npos = c.npos.as<int32_t>();

@@ -898,6 +898,7 @@ void closure_apply(Ctx& c, int algo, int n_p, const int32_t* counts, int iterati
 
 }  // namespace fc
 
+#include "analysis.h"     // what the headers below share: support bins, the wave-aggregated add, the phase timer
 #include "score.h"   // partition scoring (fc_score_*): its kernels use the helpers above
 #include "components.h"   // consensus partition (fc_consensus_support / fc_consensus_partition)
 #include "levels.h"       // consensus hierarchy (fc_consensus_levels / fc_consensus_cut)

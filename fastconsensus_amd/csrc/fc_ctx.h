@@ -99,6 +99,9 @@ struct Timer {
     size_t next = 0;
 };
 
+// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms, written by analysis.h's PhaseMarks)
+constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2;
+
 struct Ctx {
     int device = 0;
     uint64_t seed = 0;
@@ -244,20 +247,20 @@ struct Ctx {
     // labels by node and by internal vertex, community sizes, support histogram, per-node sums
     // device time of the last call's phases (timing enabled): support, histogram, components,
     // renumber + sizes, node sums
-    double cp_ms[5] = {0, 0, 0, 0, 0};
+    double cp_ms[CP_PHASES] = {};
     DevBuf cp_sup, cp_parent, cp_flag, cp_rank, cp_lab, cp_labi, cp_size, cp_hist, cp_nin, cp_nout;
     // consensus hierarchy (levels.h): the tree of the last successful fc_consensus_levels (birth, up
     // by node; lv_valid until the next fc_load_graph) and its scratch: slice cursors, edge ids by
     // support, degree sums by root, sharded per-level counters and their fold, join-level weights
     // device time of the last call's phases (timing enabled): bucket, tree, statistics, join levels
-    double lv_ms[4] = {0, 0, 0, 0};
+    double lv_ms[LV_PHASES] = {};
     DevBuf lv_birth, lv_up, lv_cursor, lv_bucket, lv_tot, lv_stats, lv_fold, lv_jw;
     bool lv_valid = false;
     int lv_nt = 0;
     // co-association (coassoc.h): the caller's node ids as uploaded, the two lists as internal
     // vertices, the count histogram
     // device time of the last call's phases (timing enabled): ids (upload + map), count
-    double ca_ms[2] = {0, 0};
+    double ca_ms[CA_PHASES] = {};
     DevBuf ca_ids, ca_va, ca_vb, ca_hist;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = getenv("FC_SCORE_SLOW") ? atoi(getenv("FC_SCORE_SLOW")) : 0;
@@ -267,10 +270,6 @@ struct Ctx {
     int64_t score_chunk = getenv("FC_SCORE_CHUNK") ? atoll(getenv("FC_SCORE_CHUNK")) : (int64_t)1 << 22;
 };
 
-struct Ctx;
-constexpr int CP_PHASES = 5;        // Ctx::cp_ms
-constexpr int LV_PHASES = 4;        // Ctx::lv_ms
-constexpr int CA_PHASES = 2;        // Ctx::ca_ms
 constexpr int FC_HPIN_I64 = 2048;   // pinned host scratch: per-sweep records (cd_rl.hip: boff | voff | n_active)
 // State the replica-lane engine hands to cd_run at the first filtered sweep of a hybrid batch
 // (FC_OPT_CD_ENGINE=2, cd_rl.hip): fill() writes it in cd.hip's layout on c.stream -- labels
@@ -382,16 +381,19 @@ int64_t count_unconverged(Ctx& c, const int32_t* w, int64_t m, int n_p);
 void score_set_reference(Ctx& c, const int32_t* labels);
 void score_partitions(Ctx& c, int graph, fc_part_score* out);
 void score_pairs(Ctx& c, const int32_t* pairs, int64_t npairs, fc_pair_score* out);
-// components.h (in consensus.hip): arguments validated by the caller
+// The analysis headers, included at the end of consensus.hip.  analysis.h holds what they share:
+// support_bin, wave_bin_add / wave_bin_rank and PhaseMarks; the union-find (cp_find, uf_hook) and the
+// opening of the partition and the hierarchy (cp_open) are components.h's, and levels.h uses them.
+// components.h: arguments validated by the caller
 void consensus_support(Ctx& c, int graph, int32_t* dev_out);
 void consensus_partition(Ctx& c, int graph, const int32_t* dev_support, int n_total, double agreement,
                          int32_t* labels_out, int64_t* hist_out, int64_t* nin_out, int64_t* nout_out,
                          fc_consensus_info* info);
-// levels.h (in consensus.hip): arguments validated by the caller
+// levels.h: arguments validated by the caller
 void consensus_levels(Ctx& c, int graph, const int32_t* dev_support, int n_total, int32_t* birth_out, int32_t* up_out,
                       fc_level_score* levels_out, int32_t* best_out);
 void consensus_cut(Ctx& c, int level, int32_t* labels_out, int64_t* k_out);
-// coassoc.h (in consensus.hip): node ids on the host, validated by the caller; b null: b = a
+// coassoc.h: node ids on the host, validated by the caller; b null: b = a
 void coassoc_matrix(Ctx& c, int64_t na, const int32_t* a, int64_t nb, const int32_t* b, int32_t* dev_out);
 void coassoc_pairs(Ctx& c, int64_t npairs, const int32_t* pairs, int32_t* dev_out);
 void coassoc_hist(Ctx& c, int64_t k, const int32_t* nodes, int64_t* hist);

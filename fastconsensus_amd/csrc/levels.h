@@ -3,8 +3,8 @@
 // connected components of the edges with support >= s; lowering s only adds edges, so the levels
 // are nested and the union-find of components.h is CONTINUED from level n_total down to level 0
 // instead of being restarted per threshold.
-// Included at the end of consensus.hip after components.h (cp_find, k_cp_hist, cp_graph, ScLabT,
-// launch_pair_partial and the scan wrapper are in scope).
+// Included at the end of consensus.hip after components.h (uf_hook, k_cp_hist, cp_graph, cp_open,
+// the helpers of analysis.h and the scan wrapper are in scope).
 //
 // Edges are bucketed by support (counting sort on k_cp_hist's histogram).  For each nonempty
 // level, from the top: one hook launch over that bucket's slice on the same parent array, then a
@@ -42,18 +42,10 @@ __global__ __launch_bounds__(256) void k_lv_bucket(int64_t m, const int32_t* __r
     for (int64_t e0 = (int64_t)blockIdx.x * blockDim.x; e0 < m; e0 += stride) {   // block-uniform trip count
         const int64_t e = e0 + threadIdx.x;
         const bool in = e < m;
-        int bin = -1;
-        if (in) {
-            const int32_t s = sup[e];
-            bin = (uint32_t)s <= (uint32_t)nt ? s : nt + 1;
-        }
+        const int bin = in ? support_bin(sup[e], nt) : -1;
         const unsigned long long act = __ballot(in);
         if (!act) continue;
-        const int src = __ffsll((long long)act) - 1;
-        const int lead = __shfl(bin, src);
-        const unsigned long long same = __ballot(in && bin == lead);
-        if (lane == src) atomicAdd(&s_cnt[lead], (unsigned int)__popcll(same));
-        if (in && bin != lead) atomicAdd(&s_cnt[bin], 1u);
+        wave_bin_add(s_cnt, in, bin, act, lane);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < nt + 2; i += blockDim.x) {
@@ -65,21 +57,10 @@ __global__ __launch_bounds__(256) void k_lv_bucket(int64_t m, const int32_t* __r
     for (int64_t e0 = (int64_t)blockIdx.x * blockDim.x; e0 < m; e0 += stride) {
         const int64_t e = e0 + threadIdx.x;
         const bool in = e < m;
-        int bin = -1;
-        if (in) {
-            const int32_t s = sup[e];
-            bin = (uint32_t)s <= (uint32_t)nt ? s : nt + 1;
-        }
+        const int bin = in ? support_bin(sup[e], nt) : -1;
         const unsigned long long act = __ballot(in);
         if (!act) continue;
-        const int src = __ffsll((long long)act) - 1;
-        const int lead = __shfl(bin, src);
-        const bool mine = in && bin == lead;
-        const unsigned long long same = __ballot(mine);
-        unsigned int r = 0;
-        if (lane == src) r = atomicAdd(&s_cnt[lead], (unsigned int)__popcll(same));
-        r = __shfl(r, src) + (unsigned int)__popcll(same & ((1ull << lane) - 1ull));
-        if (in && !mine) r = atomicAdd(&s_cnt[bin], 1u);
+        const unsigned int r = wave_bin_rank(s_cnt, in, bin, act, lane);
         if (in) bucket[s_base[bin] + r] = (int32_t)e;   // inside the bin's slice of [0, m)
     }
 }
@@ -115,24 +96,14 @@ __global__ __launch_bounds__(256) void k_lv_init(int64_t N, const int32_t* __res
     __syncthreads();
     if (threadIdx.x < 4 && s_l[threadIdx.x]) atomicAdd(shard(stats, LV_F, 3 + threadIdx.x), s_l[threadIdx.x]);
 }
-// k_cp_hook over one bucket's slice of edge ids
+// k_cp_hook over one bucket's slice of edge ids: the same union-find (uf_hook), continued
 __global__ __launch_bounds__(256) void k_lv_hook(int64_t cnt, const int32_t* __restrict__ ids,
                                                  const int32_t* __restrict__ eu, const int32_t* __restrict__ ev,
                                                  const int32_t* __restrict__ npos, int32_t* parent) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= cnt) return;
     const int32_t e = ids[i];
-    int32_t a = npos[eu[e]], b = npos[ev[e]];
-    for (;;) {
-        a = cp_find(parent, a);
-        b = cp_find(parent, b);
-        if (a == b) break;
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        const int32_t old = atomicCAS(parent + hi, hi, lo);
-        if (old == hi) break;
-        a = old;   // hi was hooked meanwhile: go on from its new parent
-        b = lo;
-    }
+    uf_hook(parent, npos[eu[e]], npos[ev[e]]);
 }
 // parent[t] <- root of t.  A node without a birth that is no root any more was a root until this
 // level: it is born at s under its root and hands over its members and degree sum.  The forest
@@ -260,27 +231,6 @@ __global__ void k_lv_label(int64_t N, const int32_t* __restrict__ root, const in
     if (t < N) lab[t] = rank[root[t]];
 }
 
-// phase boundaries of one call as events of the timing pool (timing enabled only)
-namespace {
-struct LvMarks {
-    Ctx& c;
-    int ev[LV_PHASES + 1];
-    int n = 0;
-    explicit LvMarks(Ctx& x) : c(x) {}
-    void mark() {
-        if (c.timer.on && n <= LV_PHASES) ev[n++] = timer_begin(c);
-    }
-    void collect() {   // after a stream synchronise
-        for (int i = 0; i < LV_PHASES; ++i) c.lv_ms[i] = 0.0;
-        for (int i = 0; i + 1 < n; ++i) {
-            float x = 0.f;
-            FC_HIP(hipEventElapsedTime(&x, c.timer.pool[ev[i]], c.timer.pool[ev[i + 1]]));
-            c.lv_ms[i] = x;
-        }
-    }
-};
-}  // namespace
-
 // fc_part_score's modularity from the exact integers, rounded at the division
 static double lv_modularity(int64_t in_weight, unsigned __int128 tot_sq, int64_t M2) {
     if (M2 == 0) return 0.0;
@@ -289,28 +239,16 @@ static double lv_modularity(int64_t in_weight, unsigned __int128 tot_sq, int64_t
     return (double)((long double)num / (long double)(W2 * W2));
 }
 
-// dev_support as in consensus_partition.  The tree stays in the context (lv_birth / lv_up) for
+// dev_support as in cp_open.  The tree stays in the context (lv_birth / lv_up) for
 // consensus_cut; outputs (any may be null) are written only when everything succeeded.
 void consensus_levels(Ctx& c, int graph, const int32_t* dev_support, int n_total, int32_t* birth_out, int32_t* up_out,
                       fc_level_score* levels_out, int32_t* best_out) {
-    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
     const Graph& g = cp_graph(c, graph);
     const int64_t N = c.N, m = g.m;
-    const int32_t* sup = dev_support;
-    if (!sup) {
-        score_require(c);
-        n_total = c.n_r;
-    }
-    FC_REQUIRE(n_total <= CP_MAX_TOTAL, FC_ELIMIT, "the consensus hierarchy handles at most 2048 replicas");
-    const int nt = n_total;
-    const int sl = timer_begin(c);
-    if (!sup) {
-        int32_t* s = ensure<int32_t>(c.cp_sup, m + 1);
-        ScLabT lt(c);
-        launch_pair_partial<false>(c, m, g.eu.as<int32_t>(), g.ev.as<int32_t>(), s);
-        sup = s;
-    }
-    LvMarks ph(c);
+    const CpInput in = cp_open(c, g, dev_support, n_total, "hierarchy");   // the count is outside the phases
+    const int32_t* sup = in.sup;
+    const int nt = in.n_total, sl = in.span;
+    PhaseMarks ph(c, c.lv_ms);
     ph.mark();
     const int32_t* npos = c.npos.as<int32_t>();
     const int32_t *eu = g.eu.as<int32_t>(), *ev = g.ev.as<int32_t>();

@@ -4,47 +4,35 @@ tests/test_gpu_coassoc_sharded.py; gloo, every rank on cuda:0).  The rank instal
 the first n_p golden LFR-1k labelings and writes <out>_<rank>.npz: the reduced matrix of the node
 lists in <out>_lists.npz and the histogram taken from the reduced square matrix.
 
-    python tests/coassoc_worker.py --rank R --world W --port P --n-p NP --lo LO --hi HI --out PREFIX
+    python -m tests.coassoc_worker --rank R --world W --port P --n-p NP --lo LO --hi HI --out PREFIX
 """
-import argparse
-import os
-import sys
+import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
+from tests.sharded import rank_main
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    for name in ("rank", "world", "port", "n-p", "lo", "hi"):
+def arguments(ap):
+    for name in ("n-p", "lo", "hi"):
         ap.add_argument("--" + name, type=int, required=True)
-    ap.add_argument("--out", required=True)
-    a = ap.parse_args()
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(a.port)
+
+
+def body(a):
     import torch
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=a.rank, world_size=a.world)
-    try:
-        import fastconsensus_amd as fc
-        from fastconsensus_amd.distributed import coassoc_hist_sharded, coassociation_sharded
-        from tests import golden_io
-        case = golden_io.load("lfr1k_louvain_np20")
-        e = case.edges_file
-        lists = np.load(a.out + "_lists.npz")
-        with fc.Engine(device=0, seed=77) as eng:
-            eng.load_graph(case.N, e[:, 0].copy(), e[:, 1].copy())
-            eng.set_labels(case.cd_batches[0][:a.n_p][a.lo:a.hi])
-            mat = coassociation_sharded(eng, lists["a"], lists["b"], device="cuda")
-            sq = coassociation_sharded(eng, lists["a"], device="cuda")
-            hist = coassoc_hist_sharded(eng, lists["a"], a.n_p, device="cuda")
-            torch.cuda.synchronize()
-            np.savez(a.out + "_%d.npz" % a.rank, matrix=mat.cpu().numpy(), square=sq.cpu().numpy(), hist=hist)
-    finally:
-        dist.destroy_process_group()
+    import fastconsensus_amd as fc
+    from fastconsensus_amd.distributed import coassoc_hist_sharded, coassociation_sharded
+    from tests import golden_io
+    case = golden_io.load("lfr1k_louvain_np20")
+    e = case.edges_file
+    lists = np.load(a.out + "_lists.npz")
+    with fc.Engine(device=0, seed=77) as eng:
+        eng.load_graph(case.N, e[:, 0].copy(), e[:, 1].copy())
+        eng.set_labels(case.cd_batches[0][:a.n_p][a.lo:a.hi])
+        mat = coassociation_sharded(eng, lists["a"], lists["b"], device="cuda")
+        sq = coassociation_sharded(eng, lists["a"], device="cuda")
+        hist = coassoc_hist_sharded(eng, lists["a"], a.n_p, device="cuda")
+        torch.cuda.synchronize()
+        np.savez(a.out + "_%d.npz" % a.rank, matrix=mat.cpu().numpy(), square=sq.cpu().numpy(), hist=hist)
 
 
 if __name__ == "__main__":
-    main()
+    rank_main(body, arguments)

@@ -3,46 +3,34 @@
 tests/test_gpu_consensus_levels_sharded.py; gloo, every rank on cuda:0).  Writes <out>_<rank>.npz:
 the rank's consensus result, and on rank 0 the labelings.
 
-    python tests/consensus_levels_worker.py --rank R --world W --port P --n-p NP --seed S --out PREFIX
+    python -m tests.consensus_levels_worker --rank R --world W --port P --n-p NP --seed S --out PREFIX
 """
-import argparse
-import os
-import sys
+import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
+from tests.sharded import rank_main
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    for name, kind in (("rank", int), ("world", int), ("port", int), ("n-p", int), ("seed", int)):
-        ap.add_argument("--" + name, type=kind, required=True)
-    ap.add_argument("--out", required=True)
-    a = ap.parse_args()
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(a.port)
+def arguments(ap):
+    ap.add_argument("--n-p", type=int, required=True)
+    ap.add_argument("--seed", type=int, required=True)
+
+
+def body(a):
     import torch
-    import torch.distributed as dist
-    dist.init_process_group("gloo", rank=a.rank, world_size=a.world)
-    try:
-        import fastconsensus_amd as fc
-        from fastconsensus_amd.distributed import run_sharded
-        from tests import golden_io
-        case = golden_io.load("lfr1k_louvain_np20")
-        e = case.edges_file
-        with fc.Engine(device=0, seed=a.seed) as eng:
-            eng.load_graph(case.N, e[:, 0].copy(), e[:, 1].copy())
-            labels, st, cons = run_sharded(eng, 0, a.n_p, 0.2, 0.02, device="cuda", consensus="best")
-            torch.cuda.synchronize()
-            rec = {k: np.asarray(v) for k, v in cons.items()}
-            if a.rank == 0:
-                rec["run_labels"] = labels
-            np.savez(a.out + "_%d.npz" % a.rank, **rec)
-    finally:
-        dist.destroy_process_group()
+    import fastconsensus_amd as fc
+    from fastconsensus_amd.distributed import run_sharded
+    from tests import golden_io
+    case = golden_io.load("lfr1k_louvain_np20")
+    e = case.edges_file
+    with fc.Engine(device=0, seed=a.seed) as eng:
+        eng.load_graph(case.N, e[:, 0].copy(), e[:, 1].copy())
+        labels, st, cons = run_sharded(eng, 0, a.n_p, 0.2, 0.02, device="cuda", consensus="best")
+        torch.cuda.synchronize()
+        rec = {k: np.asarray(v) for k, v in cons.items()}
+        if a.rank == 0:
+            rec["run_labels"] = labels
+        np.savez(a.out + "_%d.npz" % a.rank, **rec)
 
 
 if __name__ == "__main__":
-    main()
+    rank_main(body, arguments)

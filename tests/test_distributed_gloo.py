@@ -3,7 +3,6 @@ bit-identical partitions and graphs to one rank (fastconsensus_amd/distributed.p
 The engine here is the oracle-backed CPU model (tests/cpu_engine.py); on the GPU the
 same driver runs the HIP engine over RCCL (tests/test_gpu_parity.py checks world=1)."""
 import os
-import socket
 import tempfile
 
 import numpy as np
@@ -13,6 +12,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from tests import golden_io
+from tests.sharded import free_port
 
 
 def _graph():
@@ -23,14 +23,6 @@ def _graph():
 def _sigma(N):
     """A fixed internal numbering (the engine draws one per seed; any permutation works)."""
     return np.random.default_rng(5).permutation(N).astype(np.int32)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, algo, n_p, tau, delta, out_path, shard_closure=False, shared_out=False):
@@ -89,7 +81,7 @@ def test_sharded_equals_single_rank(world, algo, n_p, tau, shard_closure, shared
     ref_labels, ref_graph, ref_st = _single(algo, n_p, tau, 0.02)
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "r0.npz")
-        mp.spawn(_worker, args=(world, _free_port(), algo, n_p, tau, 0.02, out, shard_closure, shared_out),
+        mp.spawn(_worker, args=(world, free_port(), algo, n_p, tau, 0.02, out, shard_closure, shared_out),
                  nprocs=world, join=True)
         z = np.load(out)
         np.testing.assert_array_equal(z["labels"], ref_labels)
@@ -134,7 +126,7 @@ def test_small_all_reduce_exact():
     world = 2
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "red")
-        mp.spawn(_reduce_worker, args=(world, _free_port(), out), nprocs=world, join=True)
+        mp.spawn(_reduce_worker, args=(world, free_port(), out), nprocs=world, join=True)
         z = [np.load(out + ".%d.npz" % r) for r in range(world)]
         for n_p in (7, 255, 300):
             kmax = np.maximum(z[0]["k%d" % n_p], z[1]["k%d" % n_p])

@@ -1,28 +1,14 @@
 """run_sharded(..., consensus=theta) over two ranks (gloo, both on the one GPU): every rank's
 consensus result equals, bit for bit, what one engine holding all n_p partitions computes."""
-import os
-import socket
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from tests import golden_io
+from tests.sharded import run_ranks
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORKER = os.path.join(ROOT, "tests", "consensus_worker.py")
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def test_two_ranks_equal_one(tmp_path):
@@ -36,21 +22,8 @@ def test_two_ranks_equal_one(tmp_path):
         eng.load_graph(case.N, e[:, 0], e[:, 1])
         labels, _ = eng.run(0, n_p, 0.2, 0.02)
         exp = eng.consensus_partition(theta)
-    port, prefix = _free_port(), str(tmp_path / "r")
-    env = dict(os.environ, OMP_NUM_THREADS="2")
-    procs = [subprocess.Popen([sys.executable, "-u", WORKER, "--rank", str(r), "--world", str(world), "--port", str(port),
-                               "--n-p", str(n_p), "--theta", str(theta), "--seed", str(seed), "--out", prefix],
-                              env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-             for r in range(world)]
-    try:
-        for r, p in enumerate(procs):          # each child under its own limit; stop at the first failure
-            out = p.communicate(timeout=120)[0].decode(errors="replace")
-            assert p.returncode == 0, "rank %d exited %s:\n%s" % (r, p.returncode, out[-3000:])
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
+    prefix = str(tmp_path / "r")
+    run_ranks("consensus_worker", [["--n-p", n_p, "--theta", theta, "--seed", seed, "--out", prefix]] * world, 120)
     z = [np.load(prefix + "_%d.npz" % r) for r in range(world)]
     np.testing.assert_array_equal(z[0]["run_labels"], labels)
     assert 1 < exp["k"] < case.N

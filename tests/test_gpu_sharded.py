@@ -2,7 +2,7 @@
 box's one MI355X over gloo (fastconsensus_amd/distributed.py; SURVEY.md §8e; the reference's
 per-iteration loop fast_consensus.py:141-202 / :260-310 and final pass :383-392).
 
-Each rank runs `tests/mr_worker.py` as its own process: its contiguous replica shard through
+Each rank runs `tests.mr_worker` as its own process: its contiguous replica shard through
 fc_cd / fc_consensus_partial at a non-zero offset, the uint8 MAX / SUM all-reduces on device
 tensors (`_all_reduce_small`), the replicated threshold / closure / repair / rebuild, and the
 final labelings either into one shared host array (`SharedOutput`, each rank its own rows,
@@ -12,20 +12,16 @@ partition_edges and final graph bit-identical to ONE rank's native fc_run, and t
 identical on every rank.  The workers are child processes (subprocess), never an exec of this
 process."""
 import os
-import socket
-import subprocess
-import sys
 import tempfile
 
 import numpy as np
 import pytest
 
+from tests.sharded import run_ranks
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WORKER = os.path.join(ROOT, "tests", "mr_worker.py")
 
 
 @pytest.fixture(scope="module")
@@ -34,14 +30,6 @@ def fcmod():
         pytest.skip("no GPU")
     import fastconsensus_amd as fc
     return fc
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _one_rank(fc, algo, n_p, tau, graph, seed, opts):
@@ -56,30 +44,13 @@ def _one_rank(fc, algo, n_p, tau, graph, seed, opts):
 
 
 def _ranks(world, algo, n_p, tau, graph, seed, shard_closure, shared_out, opts, d):
-    port = _free_port()
     prefix = os.path.join(d, "r")
-    env = dict(os.environ, OMP_NUM_THREADS="2")
-    procs = []
-    for r in range(world):
-        cmd = [sys.executable, "-u", WORKER, "--rank", str(r), "--world", str(world), "--port", str(port),
-               "--algo", str(algo), "--n-p", str(n_p), "--tau", str(tau), "--graph", graph, "--seed", str(seed),
-               "--out", prefix]
-        cmd += ["--shard-closure"] if shard_closure else []
-        cmd += ["--shared-out"] if shared_out else []
-        for k, val in opts.items():
-            cmd += ["--opt", "%s=%d" % (k, val)]
-        procs.append(subprocess.Popen(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = []
-    try:
-        for p in procs:
-            outs.append(p.communicate(timeout=240)[0].decode(errors="replace"))
-    finally:
-        for p in procs:
-            if p.poll() is None:
-                p.kill()
-                p.wait()
-    for r, (p, o) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0, "rank %d exited %s:\n%s" % (r, p.returncode, o[-3000:])
+    args = ["--algo", algo, "--n-p", n_p, "--tau", tau, "--graph", graph, "--seed", seed, "--out", prefix]
+    args += ["--shard-closure"] if shard_closure else []
+    args += ["--shared-out"] if shared_out else []
+    for k, val in opts.items():
+        args += ["--opt", "%s=%d" % (k, val)]
+    run_ranks("mr_worker", [args] * world, 240)
     return [np.load(prefix + "_%d.npz" % r) for r in range(world)]
 
 

@@ -4,7 +4,7 @@
 
 Compiles the file for gfx950, device side only, with the flags of fastconsensus_amd/build.py plus
 -Rpass-analysis=kernel-resource-usage, and prints one line per kernel: VGPRs, SGPR spills, VGPR
-spills, scratch bytes per lane, waves per SIMD, name (demangled where c++filt / llvm-cxxfilt is
+spills, scratch bytes per lane, waves per SIMD, static LDS bytes per block, name (demangled where c++filt / llvm-cxxfilt is
 found).  Nothing but the remarks is read: no object file is kept, no assembly is inspected.
 """
 import argparse
@@ -91,11 +91,11 @@ def main():
     for k, n in zip(ks, demangle([k["name"] for k in ks])):
         k["name"] = short(n)
     print("# %s for %s%s" % (a.src, fb.ARCH, "".join(" -D" + d for d in a.defines)))
-    print("# %5s %7s %7s %7s %4s  %s" % ("VGPRs", "S-spill", "V-spill", "scratch", "occ", "kernel"))
+    print("# %5s %7s %7s %7s %4s %6s  %s" % ("VGPRs", "S-spill", "V-spill", "scratch", "occ", "LDS", "kernel"))
     for k in ks:
         if a.filter in k["name"]:
-            print("  %5d %7d %7d %7d %4d  %s" % (k.get("vgpr", -1), k.get("sspill", -1), k.get("vspill", -1),
-                                               k.get("scratch", -1), k.get("occ", -1), k["name"]))
+            print("  %5d %7d %7d %7d %4d %6d  %s" % (k.get("vgpr", -1), k.get("sspill", -1), k.get("vspill", -1),
+                                                   k.get("scratch", -1), k.get("occ", -1), k.get("lds", -1), k["name"]))
 
 
 if __name__ == "__main__":
