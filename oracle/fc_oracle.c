@@ -1370,6 +1370,378 @@ void orc_engine_leiden(i64 N, const i64* rowptr, const i32* col, const i32* cw, 
     free(kdeg);
 }
 
+/* ==================================================================================
+ * CPU twin of the engine's multi-level Infomap (leiden.hip, infomap_run / multilevel(c, info =
+ * true, ...)), label-for-label target for the MODE_INFO instances of its kernels.  One union
+ * replica (local replica r, trial j) at a time, in LOCAL ids, written from leiden.hip alone:
+ *   start      singleton modules on the topology (weights ignored): kv = sv = row length, M2 = 2m;
+ *   pass sw    of level l: bucket(x) = hash32(key ^ hash32(x)) % B with key = stream_key(seed,
+ *              replica, iteration, l * 4096 + sw, 16 + 2 + 8 * trial); a bucket's vertices decide
+ *              against the state the earlier buckets left, then their moves apply together; a
+ *              vertex moves to the neighbour module of the smallest map-equation change if that
+ *              change is below -1e-10 (order: delta, larger tie hash, smaller id); the passes of
+ *              a level end with the first one that moves nothing (or at max_sweeps);
+ *   aggregate  when the modules are fewer than the level's nodes: new ids = scan of the non-empty
+ *              modules in id order; rows through nid[P[.]], self loops dropped, weights summed;
+ *              the new node has kv = module flow, sv = its row's weight sum, and is a singleton
+ *              module; otherwise (or at level 63) the level's P is final: lab[v] = P[memb[v]];
+ *   trials     the earliest trial of strictly smallest codelength.
+ *
+ * What the twin does NOT restate is the code under test:
+ *   - applies are by RECOMPUTATION: after a bucket's moves every module's flow and exit weight and
+ *     the total exit weight Q are recomputed from P and the level graph from scratch (the device
+ *     keeps them incrementally: lv_move's exit-weight bookkeeping under simultaneous moves);
+ *   - deltas are in long double (log2l, p = x / M2 formed in long double); the device's are
+ *     doubles with fc_log2 and p = x * (1 / M2).
+ * All Infomap STATE is integer (module flow and exit weight, Q, P), so the two agree exactly
+ * wherever a decision is not a near-tie.  Candidates are ranked in two stages: candidates whose
+ * integer inputs (exit_B, flow_B, w_to_B) are identical are an EXACT tie -- the device evaluates one
+ * pure function on identical arguments, so its doubles are identical too -- resolved by hash, then
+ * id; all others are ordered by the long double value.  A decision is counted AMBIGUOUS when a
+ * candidate with different integer inputs lies within IT_EPS of the best delta, or the best delta
+ * lies within IT_EPS of the threshold -1e-10.  The tests run on inputs where the twin counts no
+ * ambiguous decision (tests/test_infomap_twin.py), so every device decision is determined.
+ * The same rule for the trials: two trials of a replica whose from-scratch codelengths differ by
+ * less than IT_CL_EPS while their partitions differ (after canonical renumbering) are an ambiguous
+ * trial choice.  Trials with EQUAL partitions are not: the device sums the modules in another
+ * order, so it may pick either, and either gives the same renumbered labels; `equiv` marks them
+ * (the final-level ids of two such trials can differ).
+ *
+ * trace (per union replica u = r * trials + j, IT_TRACE int64): [0] levels; [1 + 8 * l + k] for
+ * level l < 64: k = 0 nodes, 1 entries, 2 longest row, 3 passes, 4 moves; then by lt_class's seven
+ * row-length classes, [2][7] each (0 the input-graph level, 1 the aggregate levels): decisions at
+ * IT_DEC, applied moves at IT_MOV; at IT_TIE decisions whose best candidates were an exact tie, the
+ * widest such tie, those of them that moved, those wider than 64 that moved; at IT_AMB the
+ * ambiguous decisions; at IT_ADJ [2] buckets in which two adjacent vertices both moved (input /
+ * aggregate levels); at IT_HELD the decisions the threshold held back: a best delta in
+ * (-1e-10, -IT_EPS), a gain too small to take, where `delta < 0` in place of the threshold would
+ * move; at IT_HELD + 1 the decisions of rows past 512 entries with weight inside their own module
+ * (k_lv_heavy's s_wown).
+ * margins (per union replica, 2 doubles): the smallest gap between the best delta and a runner-up
+ * with different integer inputs, and between a best delta and -1e-10.
+ * ================================================================================== */
+#define IT_DEC (1 + 8 * LT_LEVELS)
+#define IT_MOV (IT_DEC + 2 * LT_NCLS)
+#define IT_TIE (IT_MOV + 2 * LT_NCLS)
+#define IT_AMB (IT_TIE + 4)
+#define IT_ADJ (IT_AMB + 1)
+#define IT_HELD (IT_ADJ + 2)
+#define IT_TRACE (IT_HELD + 2)
+int orc_infomap_trace_len(void) { return IT_TRACE; }
+/* IT_EPS from the device's absolute error in one delta (u = 1.1e-16, one double rounding).  A
+ * delta is 11 terms t = p * log2(p), |t| <= 0.531 (the maximum of -p log2 p, at p = 1/e), four of
+ * them doubled.  Per term: fc_log2 is within 2.5 ulp (tests/test_fc_log2.py): 2.5u|t| <= 1.5e-16;
+ * p = x * inv carries the roundings of inv and of the product, 2u relative, which dt/dp = log2 p +
+ * 1/ln 2 turns into 2u |t + p / ln 2| <= 1.2e-16 + 3.2e-16 p; the product p * log2 p one more u|t|.
+ * That is <= 3.3e-16 + 3.2e-16 p per term, 15 weighted terms, and the ten additions add at most u
+ * of a partial sum (|sum| < 1.1) each: in all about 5e-15 for the module flows of a real partition
+ * (the p of one delta sum to well below 2), below 1e-14 for any p.  The twin's own long double
+ * error is 2000 times smaller.  IT_EPS is 100 to 200 times the device's bound: derived, never
+ * tuned to a case; a case that counts an ambiguous decision gets another seed. */
+#define IT_EPS 1e-12L
+#define IT_CL_EPS 1e-9L     /* trial codelengths: sums over up to N modules, the same per-term error */
+#define IT_MIN_GAIN 1e-10   /* leiden.hip INFO_MIN_GAIN (the double constant) */
+typedef struct { i64 n, E; i64* rp; i32* col; i32* w; i64* kv; i64* sv; i64 maxdeg; } it_graph;
+static inline long double it_plogp(long long x, long double M2) {
+    if (x <= 0) return 0.0L;
+    const long double p = (long double)x / M2;
+    return p * log2l(p);
+}
+/* flow, exit weight of every module and Q from P and the level graph, from scratch */
+static long long it_recompute(const it_graph* g, const i32* P, i64* flow, i64* ext, i32* msize) {
+    const i64 n = g->n;
+    for (i64 c = 0; c < n; ++c) { flow[c] = 0; ext[c] = 0; msize[c] = 0; }
+    for (i64 x = 0; x < n; ++x) {
+        const i32 c = P[x];
+        flow[c] += g->kv[x];
+        msize[c]++;
+        i64 in = 0;
+        for (i64 j = g->rp[x]; j < g->rp[x + 1]; ++j)
+            if (P[g->col[j]] == c) in += g->w ? g->w[j] : 1;
+        ext[c] += g->sv[x] - in;
+    }
+    long long Q = 0;
+    for (i64 c = 0; c < n; ++c) Q += ext[c];
+    return Q;
+}
+static long double it_codelength(i64 n, const i64* flow, const i64* ext, const i32* msize, long long Q,
+                                 long double M2) {
+    long double L = it_plogp(Q, M2);
+    for (i64 c = 0; c < n; ++c)
+        if (msize[c] > 0) L += -2.0L * it_plogp(ext[c], M2) + it_plogp(ext[c] + flow[c], M2);
+    return L;
+}
+
+static long double it_replica(i64 N, const i64* rowptr, const i32* col, u64 seed, uint32_t rg, uint32_t iter,
+                              uint32_t trial, int B, int max_sweeps, i32* lab, i64* tr, double* margins) {
+    memset(tr, 0, sizeof(i64) * IT_TRACE);
+    const long double M2 = (long double)rowptr[N];
+    it_graph g;
+    g.n = N; g.E = rowptr[N]; g.rp = (i64*)rowptr; g.col = (i32*)col; g.w = NULL; g.maxdeg = 0;
+    g.kv = (i64*)malloc(sizeof(i64) * (size_t)(N ? N : 1));
+    g.sv = (i64*)malloc(sizeof(i64) * (size_t)(N ? N : 1));
+    for (i64 v = 0; v < N; ++v) {
+        g.kv[v] = g.sv[v] = rowptr[v + 1] - rowptr[v];
+        if (g.kv[v] > g.maxdeg) g.maxdeg = g.kv[v];
+    }
+    int owned = 0;   /* g's rp / col / w are this function's (levels >= 1) */
+    const size_t NN = (size_t)(N ? N : 1);
+    i32* P = (i32*)malloc(sizeof(i32) * NN);
+    i64* flow = (i64*)malloc(sizeof(i64) * NN);
+    i64* ext = (i64*)malloc(sizeof(i64) * NN);
+    i32* msize = (i32*)malloc(sizeof(i32) * NN);
+    i32* memb = (i32*)malloc(sizeof(i32) * NN);
+    i32* nid = (i32*)malloc(sizeof(i32) * (NN + 1));
+    i32* moff = (i32*)malloc(sizeof(i32) * (NN + 2));
+    i32* mlist = (i32*)malloc(sizeof(i32) * NN);
+    i64* acc = (i64*)calloc(NN, sizeof(i64));
+    u8* seen = (u8*)calloc(NN, 1);
+    i32* keys = (i32*)malloc(sizeof(i32) * NN);
+    long double* dl = (long double*)malloc(sizeof(long double) * NN);
+    i32* mv = (i32*)malloc(sizeof(i32) * NN);
+    i32* mt = (i32*)malloc(sizeof(i32) * NN);
+    i32* bk = (i32*)malloc(sizeof(i32) * NN);
+    u8* mark = (u8*)calloc(NN, 1);
+    for (i64 v = 0; v < N; ++v) { P[v] = (i32)v; memb[v] = (i32)v; }
+    double m_run = 1e300, m_thr = 1e300;
+    long double L = 0.0L;
+    int level = 0;
+    for (;; ++level) {
+        const i64 n = g.n;
+        const int lm = level == 0 ? 0 : 1;
+        long long Q = it_recompute(&g, P, flow, ext, msize);
+        i64 lmoves = 0;
+        int sw = 0;
+        for (; sw < max_sweeps;) {
+            const uint32_t key = tw_stream_key(seed, rg, iter, (uint32_t)(level * 4096 + sw), 16 + 2 + 8 * trial);
+            for (i64 x = 0; x < n; ++x) bk[x] = (i32)(tw_hash32(key ^ tw_hash32((uint32_t)x)) % (uint32_t)B);
+            i64 pmoves = 0;
+            for (int b = 0; b < B; ++b) {
+                i64 nm = 0;
+                for (i64 x = 0; x < n; ++x) {
+                    if (bk[x] != b) continue;
+                    const i64 rb = g.rp[x], re = g.rp[x + 1];
+                    tr[IT_DEC + lm * LT_NCLS + lt_class(re - rb)]++;
+                    const i32 own = P[x];
+                    long long wown = 0;
+                    i64 nk = 0;
+                    for (i64 j = rb; j < re; ++j) {
+                        const i32 c = P[g.col[j]];
+                        const i32 w = g.w ? g.w[j] : 1;
+                        if (c == own) { wown += w; continue; }
+                        if (!seen[c]) { seen[c] = 1; acc[c] = 0; keys[nk++] = c; }
+                        acc[c] += w;
+                    }
+                    if (wown > 0 && re - rb > 512) tr[IT_HELD + 1]++;
+                    if (!nk) continue;
+                    /* leiden.hip info_a / info_b, in long double */
+                    const long long kvx = g.kv[x], svx = g.sv[x];
+                    const long long oA = ext[own], tA = flow[own];
+                    const long long oA2 = oA - svx + 2 * wown, tA2 = tA - kvx, dA = oA2 - oA;
+                    const long double termA = -2.0L * (it_plogp(oA2, M2) - it_plogp(oA, M2)) +
+                                              (it_plogp(oA2 + tA2, M2) - it_plogp(oA + tA, M2));
+                    const long double q0 = it_plogp(Q, M2);
+                    i64 qb = -1;
+                    for (i64 q = 0; q < nk; ++q) {
+                        const i32 c = keys[q];
+                        const long long oB = ext[c], tB = flow[c];
+                        const long long oB2 = oB + svx - 2 * (long long)acc[c], tB2 = tB + kvx;
+                        const long long Q2 = Q + dA + (oB2 - oB);
+                        dl[q] = (it_plogp(Q2, M2) - q0) + termA - 2.0L * (it_plogp(oB2, M2) - it_plogp(oB, M2)) +
+                                (it_plogp(oB2 + tB2, M2) - it_plogp(oB + tB, M2));
+                        if (qb < 0 || dl[q] < dl[qb]) qb = q;
+                        seen[c] = 0;
+                    }
+                    /* stage 1: the candidates whose integer inputs equal the best's are an exact tie,
+                     * by hash then id; stage 2: everyone else by the long double value */
+                    const i32 c0 = keys[qb];
+                    i32 bc = -1; uint32_t bh = 0;
+                    i64 width = 0;
+                    int amb = 0;
+                    for (i64 q = 0; q < nk; ++q) {
+                        const i32 c = keys[q];
+                        if (ext[c] == ext[c0] && flow[c] == flow[c0] && acc[c] == acc[c0]) {
+                            const uint32_t h = lt_tie(key, x, c);
+                            if (bc < 0 || h > bh || (h == bh && c < bc)) { bc = c; bh = h; }
+                            ++width;
+                        } else {
+                            const long double gap = dl[q] - dl[qb];
+                            if ((double)gap < m_run) m_run = (double)gap;
+                            if (gap <= IT_EPS) amb = 1;
+                        }
+                    }
+                    const long double bd = dl[qb];
+                    const long double tg = fabsl(bd + (long double)IT_MIN_GAIN);
+                    if ((double)tg < m_thr) m_thr = (double)tg;
+                    if (tg <= IT_EPS) amb = 1;
+                    tr[IT_AMB] += amb;
+                    const int moves = bd < -(long double)IT_MIN_GAIN;
+                    if (!moves && bd < -IT_EPS) tr[IT_HELD]++;
+                    if (width > 1) {
+                        tr[IT_TIE]++;
+                        if (width > tr[IT_TIE + 1]) tr[IT_TIE + 1] = width;
+                        if (moves) { tr[IT_TIE + 2]++; if (width > 64) tr[IT_TIE + 3]++; }
+                    }
+                    if (moves) { mv[nm] = (i32)x; mt[nm] = bc; ++nm; }
+                }
+                if (!nm) continue;
+                for (i64 i = 0; i < nm; ++i) {
+                    P[mv[i]] = mt[i];
+                    mark[mv[i]] = 1;
+                    tr[IT_MOV + lm * LT_NCLS + lt_class(g.rp[mv[i] + 1] - g.rp[mv[i]])]++;
+                }
+                int adj = 0;
+                for (i64 i = 0; i < nm && !adj; ++i)
+                    for (i64 j = g.rp[mv[i]]; j < g.rp[mv[i] + 1]; ++j)
+                        if (mark[g.col[j]]) { adj = 1; break; }
+                tr[IT_ADJ + lm] += adj;
+                for (i64 i = 0; i < nm; ++i) mark[mv[i]] = 0;
+                Q = it_recompute(&g, P, flow, ext, msize);   /* the apply: from scratch */
+                pmoves += nm;
+            }
+            ++sw;
+            lmoves += pmoves;
+            if (pmoves == 0) break;
+        }
+        if (level < LT_LEVELS) {
+            i64* t = tr + 1 + 8 * level;
+            t[0] = n; t[1] = g.E; t[2] = g.maxdeg; t[3] = sw; t[4] = lmoves;
+        }
+        /* ---- modules < level nodes: aggregate by modules; else this level's P is final */
+        i32 nn = 0;
+        for (i64 c = 0; c < n; ++c) { nid[c] = nn; nn += msize[c] > 0; }
+        nid[n] = nn;
+        if (nn == n || level + 1 >= LT_LEVELS) {
+            L = it_codelength(n, flow, ext, msize, Q, M2);
+            break;
+        }
+        it_graph nx;
+        nx.n = nn;
+        nx.rp = (i64*)malloc(sizeof(i64) * (size_t)(nn + 1));
+        nx.kv = (i64*)malloc(sizeof(i64) * (size_t)nn);
+        nx.sv = (i64*)malloc(sizeof(i64) * (size_t)nn);
+        for (i64 c = 0; c < n; ++c) if (msize[c] > 0) nx.kv[nid[c]] = flow[c];
+        for (i32 k = 0; k <= nn + 1; ++k) moff[k] = 0;
+        for (i64 x = 0; x < n; ++x) moff[nid[P[x]] + 2]++;
+        for (i32 k = 0; k < nn; ++k) moff[k + 2] += moff[k + 1];
+        for (i64 x = 0; x < n; ++x) mlist[moff[nid[P[x]] + 1]++] = (i32)x;
+        const i64 cap = g.E > 0 ? g.E : 1;
+        i64 E = 0;
+        nx.col = (i32*)malloc(sizeof(i32) * (size_t)cap);
+        nx.w = (i32*)malloc(sizeof(i32) * (size_t)cap);
+        nx.maxdeg = 0;
+        for (i32 xn = 0; xn < nn; ++xn) {
+            nx.rp[xn] = E;
+            i64 nk = 0, rs = 0;
+            for (i32 q = moff[xn]; q < moff[xn + 1]; ++q) {
+                const i32 x = mlist[q];
+                for (i64 j = g.rp[x]; j < g.rp[x + 1]; ++j) {
+                    const i32 yn = nid[P[g.col[j]]];
+                    if (yn == xn) continue;
+                    if (!seen[yn]) { seen[yn] = 1; acc[yn] = 0; keys[nk++] = yn; }
+                    acc[yn] += g.w ? g.w[j] : 1;
+                }
+            }
+            for (i64 q = 0; q < nk; ++q) {
+                nx.col[E] = keys[q]; nx.w[E] = (i32)acc[keys[q]]; rs += acc[keys[q]]; seen[keys[q]] = 0; ++E;
+            }
+            nx.sv[xn] = rs;   /* the new node's external weight: its row's weight sum */
+            if (nk > nx.maxdeg) nx.maxdeg = nk;
+        }
+        nx.rp[nn] = E;
+        nx.E = E;
+        for (i64 v = 0; v < N; ++v) memb[v] = nid[P[memb[v]]];
+        for (i32 k = 0; k < nn; ++k) P[k] = k;
+        if (owned) { free(g.rp); free(g.col); free(g.w); }
+        free(g.kv); free(g.sv);
+        g = nx;
+        owned = 1;
+    }
+    tr[0] = level + 1;
+    for (i64 v = 0; v < N; ++v) lab[v] = P[memb[v]];
+    margins[0] = m_run; margins[1] = m_thr;
+    if (owned) { free(g.rp); free(g.col); free(g.w); }
+    free(g.kv); free(g.sv);
+    free(P); free(flow); free(ext); free(msize); free(memb); free(nid); free(moff); free(mlist); free(acc); free(seen);
+    free(keys); free(dl); free(mv); free(mt); free(bk); free(mark);
+    return L;
+}
+
+/* 1 when the labelings a and b are the same partition */
+static int it_same_partition(i64 N, const i32* a, const i32* b, i32* ma, i32* mb) {
+    for (i64 v = 0; v < N; ++v) ma[v] = mb[v] = -1;
+    for (i64 v = 0; v < N; ++v) {
+        if (ma[a[v]] < 0 && mb[b[v]] < 0) { ma[a[v]] = b[v]; mb[b[v]] = a[v]; }
+        else if (ma[a[v]] != b[v] || mb[b[v]] != a[v]) return 0;
+    }
+    return 1;
+}
+
+/* Replicas [rbase, rbase + n_r) of the engine's Infomap, `trials` trials each, on the topology of a
+ * symmetric CSR (weights are not read).  buckets: FC_OPT_BUCKETS (0: 32).
+ *   tlab    [n_r][trials][N] every trial's labels (local ids of its final level, as k_lv_final writes them)
+ *   tcl     [n_r][trials] every trial's from-scratch codelength (bits, without the constant node term)
+ *   best    [n_r] the chosen trial: the earliest of strictly smallest codelength
+ *   equiv   [n_r][trials] 1 for the chosen trial and for every trial with the SAME partition and a
+ *           codelength within IT_CL_EPS of it (the device may pick any of them)
+ *   amb     [n_r] ambiguous trial choices: pairs of trials within IT_CL_EPS whose partitions differ
+ *   trace   [n_r * trials][IT_TRACE], margins [n_r * trials][2]
+ *   partial [2] passes run by some but not all of the batch's union replicas at that level: the
+ *           input-graph level (the device's per-replica launch map), the aggregate levels */
+void orc_engine_infomap(i64 N, const i64* rowptr, const i32* col, int n_r, int rbase, int iteration, u64 seed,
+                        int trials, int buckets, int max_sweeps, i32* tlab, double* tcl, i32* best, u8* equiv,
+                        i32* amb, i64* trace, double* margins, i64* partial) {
+    const int B = buckets > 0 ? buckets : 32;
+    const int nu = n_r * trials;
+    long double* cl = (long double*)malloc(sizeof(long double) * (size_t)(nu ? nu : 1));
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int u = 0; u < nu; ++u)
+        cl[u] = it_replica(N, rowptr, col, seed, (uint32_t)(rbase + u / trials), (uint32_t)iteration,
+                           (uint32_t)(u % trials), B, max_sweeps, tlab + (i64)u * N, trace + (i64)u * IT_TRACE,
+                           margins + 2 * (i64)u);
+    i32* ma = (i32*)malloc(sizeof(i32) * (size_t)(N ? N : 1));
+    i32* mb = (i32*)malloc(sizeof(i32) * (size_t)(N ? N : 1));
+    for (int r = 0; r < n_r; ++r) {
+        const long double* c = cl + (i64)r * trials;
+        int jb = 0;
+        for (int j = 1; j < trials; ++j) if (c[j] < c[jb]) jb = j;
+        best[r] = jb;
+        amb[r] = 0;
+        for (int j = 0; j < trials; ++j) {
+            tcl[(i64)r * trials + j] = (double)c[j];
+            equiv[(i64)r * trials + j] = j == jb;
+            for (int k = j + 1; k < trials; ++k) {
+                if (fabsl(c[j] - c[k]) >= IT_CL_EPS) continue;
+                const int same = it_same_partition(N, tlab + ((i64)r * trials + j) * N, tlab + ((i64)r * trials + k) * N,
+                                                   ma, mb);
+                if (!same) amb[r]++;
+            }
+        }
+        for (int j = 0; j < trials; ++j)
+            if (j != jb && fabsl(c[j] - c[jb]) < IT_CL_EPS &&
+                it_same_partition(N, tlab + ((i64)r * trials + j) * N, tlab + ((i64)r * trials + jb) * N, ma, mb))
+                equiv[(i64)r * trials + j] = 1;
+    }
+    /* passes of a level that only part of the batch still ran */
+    partial[0] = partial[1] = 0;
+    for (int l = 0; l < LT_LEVELS; ++l) {
+        i64 present = 0, maxp = 0;
+        for (int u = 0; u < nu; ++u) {
+            const i64* t = trace + (i64)u * IT_TRACE;
+            if (l < t[0]) { ++present; if (t[1 + 8 * l + 3] > maxp) maxp = t[1 + 8 * l + 3]; }
+        }
+        for (i64 sw = 0; sw < maxp; ++sw) {
+            i64 run = 0;
+            for (int u = 0; u < nu; ++u) {
+                const i64* t = trace + (i64)u * IT_TRACE;
+                run += l < t[0] && sw < t[1 + 8 * l + 3];
+            }
+            if (run > 0 && run < present) partial[l ? 1 : 0]++;
+        }
+    }
+    free(cl); free(ma); free(mb);
+}
+
 /* CPU twin of the engine's counter-based closure sampler (consensus.hip k_closure_sample):
  * attempt t draws Philox4x32-10(counter = {t_lo, t_hi, iteration, 0x5eed}); node
  * x = uniform over N; if x has >= 2 neighbours in the post-threshold CSR (sorted rows),

@@ -80,6 +80,11 @@ def lib():
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int, _i32p, _i64p]
         L.orc_leiden_trace_len.restype = ctypes.c_int
+        _f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+        L.orc_engine_infomap.argtypes = [i64, _i64p, _i32p, ctypes.c_int, ctypes.c_int, ctypes.c_int, u64,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, _i32p, _f64p, _i32p, _u8p, _i32p,
+                                         _i64p, _f64p, _i64p]
+        L.orc_infomap_trace_len.restype = ctypes.c_int
         L.orc_device_sigma.argtypes = [i64, u64, _i32p]
         L.orc_set_lpa_ties.argtypes = [ctypes.c_int]
         L.orc_set_lpa_coarsen.argtypes = [ctypes.c_int]
@@ -377,6 +382,99 @@ def engine_leiden(g, n_r, rbase, iteration, seed, buckets=0, level_buckets=LEVEL
     lib().orc_engine_leiden(g.N, rowptr, col, cw, n_r, rbase, iteration, int(seed) & (2**64 - 1), int(buckets or 0),
                             level_buckets, max_sweeps, chunk, prune, coarsen, prune_mark, lab, tr)
     return lab, [LeidenTrace(t) for t in tr]
+
+
+INFOMAP_MODES = ("input", "aggregate")   # the input-graph level, the aggregate levels
+INFOMAP_TRIAL_EPS = 1e-9                 # fc_oracle.c IT_CL_EPS
+
+
+class InfomapTrace:
+    """One trial's trace of engine_infomap: `levels`; per level `nodes`, `entries`, `longest_row`,
+    `passes`, `moves`; `decisions[mode][class]` and `moved[mode][class]` (modes INFOMAP_MODES,
+    classes LEIDEN_CLASSES); `ties` (decisions whose best candidates were an exact tie),
+    `widest_tie`, `ties_moved`, `wide_ties_moved` (wider than 64, and moved); `ambiguous`
+    decisions; `adjacent_movers[mode]` (buckets in which two adjacent vertices both moved);
+    `held_negative` (decisions with a best delta inside (-1e-10, -EPS): a gain too small to take,
+    held back by the threshold, where `delta < 0` would move);
+    `heavy_own_weight` (decisions of rows past 512 entries with weight inside their own module);
+    `margin_runner_up`, `margin_threshold` (the smallest gaps seen, bits)."""
+
+    def __init__(self, t, margins):
+        self.levels = int(t[0])
+        lv = t[1:1 + 8 * 64].reshape(64, 8)[:self.levels]
+        self.nodes, self.entries, self.longest_row, self.passes, self.moves = (lv[:, k].copy() for k in range(5))
+        o = 1 + 8 * 64
+        self.decisions = t[o:o + 14].reshape(2, 7).copy()
+        self.moved = t[o + 14:o + 28].reshape(2, 7).copy()
+        self.ties, self.widest_tie, self.ties_moved, self.wide_ties_moved = (int(x) for x in t[o + 28:o + 32])
+        self.ambiguous = int(t[o + 32])
+        self.adjacent_movers = t[o + 33:o + 35].copy()
+        self.held_negative, self.heavy_own_weight = int(t[o + 35]), int(t[o + 36])
+        self.margin_runner_up, self.margin_threshold = float(margins[0]), float(margins[1])
+
+    def summary(self):
+        cls = lambda a: "+".join(LEIDEN_CLASSES[k] for k in range(7) if a[k]) or "-"
+        return ("%d levels, longest rows %s, passes %s, decided %s, moved %s, ties %d (widest %d), "
+                "held below zero %d, ambiguous %d, margins %.3g / %.3g" % (
+                    self.levels, list(map(int, self.longest_row)), list(map(int, self.passes)),
+                    " ".join("%s:%s" % (m, cls(self.decisions[i])) for i, m in enumerate(INFOMAP_MODES)),
+                    " ".join("%s:%s" % (m, cls(self.moved[i])) for i, m in enumerate(INFOMAP_MODES)),
+                    self.ties, self.widest_tie, self.held_negative, self.ambiguous, self.margin_runner_up,
+                    self.margin_threshold))
+
+
+class InfomapTwin:
+    """engine_infomap's result.  `labels` [n_r][N]: the chosen trial's labels (local ids of its
+    final level); `codelength` [n_r] (bits, without the constant node term); `trial_labels`
+    [n_r][trials][N], `trial_codelength` [n_r][trials], `best` [n_r]; `equivalent` [n_r][trials]:
+    the chosen trial and every trial of the same partition within INFOMAP_TRIAL_EPS of it (the
+    device, which sums the modules in another order, may pick any of them: the same renumbered
+    labels, possibly other final-level ids); `ambiguous_trials` [n_r]; `traces` [n_r][trials];
+    `partial_passes` [2] (input-graph level, aggregate levels)."""
+
+    def __init__(self, tlab, tcl, best, equiv, amb, traces, partial):
+        self.trial_labels, self.trial_codelength, self.best = tlab, tcl, best
+        self.equivalent, self.ambiguous_trials = equiv.astype(bool), amb
+        self.traces, self.partial_passes = traces, partial
+        r = np.arange(len(best))
+        self.labels, self.codelength = tlab[r, best], tcl[r, best]
+
+    def all_traces(self):
+        return [t for row in self.traces for t in row]
+
+    def ambiguous(self):
+        """(ambiguous decisions, ambiguous trial choices) of the whole batch."""
+        return sum(t.ambiguous for t in self.all_traces()), int(self.ambiguous_trials.sum())
+
+    def decisions(self):
+        return sum(t.decisions for t in self.all_traces())
+
+    def moved(self):
+        return sum(t.moved for t in self.all_traces())
+
+    def accepts(self, r, labels):
+        """Whether `labels` [N] are replica r's: the labels of one of its equivalent trials."""
+        return any(np.array_equal(labels, self.trial_labels[r, j]) for j in np.flatnonzero(self.equivalent[r]))
+
+
+def engine_infomap(g, n_r, rbase, iteration, seed, trials=10, buckets=0, max_sweeps=200):
+    """CPU twin of the engine's multi-level Infomap (leiden.hip MODE_INFO; label-for-label target
+    wherever it counts no ambiguity): replicas [rbase, rbase + n_r) of `trials` trials on g's
+    topology (weights ignored).  buckets = FC_OPT_BUCKETS (0: the engine's 32).  -> InfomapTwin."""
+    rowptr, col, _ = g.csr()
+    nu = n_r * trials
+    tlab = np.empty((n_r, trials, g.N), np.int32)
+    tcl = np.empty((n_r, trials), np.float64)
+    best, amb = np.empty(n_r, np.int32), np.empty(n_r, np.int32)
+    equiv = np.empty((n_r, trials), np.uint8)
+    tl = lib().orc_infomap_trace_len()
+    tr = np.zeros((nu, tl), np.int64)
+    mg = np.zeros((nu, 2), np.float64)
+    partial = np.zeros(2, np.int64)
+    lib().orc_engine_infomap(g.N, rowptr, col, n_r, rbase, iteration, int(seed) & (2**64 - 1), trials, int(buckets or 0),
+                             max_sweeps, tlab, tcl, best, equiv, amb, tr, mg, partial)
+    traces = [[InfomapTrace(tr[r * trials + j], mg[r * trials + j]) for j in range(trials)] for r in range(n_r)]
+    return InfomapTwin(tlab, tcl, best, equiv, amb, traces, partial)
 
 
 def renumber(labels):

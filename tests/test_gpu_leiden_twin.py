@@ -5,8 +5,10 @@ Everything is integer, so there are no tolerances.  That each graph reaches the 
 for is asserted from the twin's trace in tests/test_leiden.py (no GPU) and confirmed here from
 the engine's own byte counters.
 
-Infomap runs on the same graphs without a twin (its deltas are floating point): range,
-determinism, sharding, and a codelength no worse than the two trivial partitions.
+Infomap runs on the same graphs here for its weak properties only: range, determinism, sharding,
+and a codelength no worse than the two trivial partitions.  Its label-for-label comparison is in
+tests/test_gpu_infomap_twin.py, against its own twin (orc_engine_infomap: all Infomap state is
+integer, and the twin counts the decisions the floating-point deltas could leave open).
 """
 import json
 import os
