@@ -34,6 +34,7 @@ SYMBOLS = [
     "fc_consensus_support", "fc_consensus_partition", "fc_consensus_timing",
     "fc_consensus_levels", "fc_consensus_cut", "fc_consensus_levels_timing",
     "fc_coassociation", "fc_coassoc_pairs", "fc_coassoc_hist", "fc_coassoc_timing",
+    "fc_cluster_consensus", "fc_cluster_consensus_timing",
 ]
 FC_SCORE_REF = -1
 SCORE_GRAPHS = {"input": 0, "working": 1}
@@ -100,6 +101,18 @@ class LevelScore(ctypes.Structure):
         ("singletons", ctypes.c_int64), ("in_weight", ctypes.c_int64), ("tot_sq_lo", ctypes.c_uint64),
         ("tot_sq_hi", ctypes.c_uint64), ("modularity", ctypes.c_double),
     ]
+
+
+class ClusterInfo(ctypes.Structure):
+    """fc_cluster_info"""
+    _fields_ = [
+        ("k", ctypes.c_int64), ("max_size", ctypes.c_int64), ("singletons", ctypes.c_int64),
+        ("pairs_total", ctypes.c_int64), ("slow_members", ctypes.c_int64), ("n_r", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
 _lib = None
@@ -170,6 +183,9 @@ def load():
     L.fc_coassoc_pairs.argtypes = [vp, i64, vp, vp]            # npairs, pairs (host), dev_out
     L.fc_coassoc_hist.argtypes = [vp, i64, vp, _i64p]          # k, nodes (host), hist int64[n_r + 1]
     L.fc_coassoc_timing.argtypes = [vp, P(dbl)]
+    # labels (host), ids_out, size_out (host or NULL), dev_cluster, dev_item (device or NULL), fc_cluster_info
+    L.fc_cluster_consensus.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.fc_cluster_consensus_timing.argtypes = [vp, P(dbl)]
     _lib = L
     return L
 

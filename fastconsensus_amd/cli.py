@@ -11,6 +11,10 @@ files hold the level of largest modularity, and ``consensus_t.../levels.tsv`` on
 ``--coassoc K`` writes, beside the output tree, ``coassoc.npy`` (the int32 [K, K] consensus matrix
 of K nodes drawn by ``numpy.random.default_rng(seed)``, ``Engine.coassociation``) and
 ``coassoc_nodes.txt`` (their labels, one per line, in the matrix's order).
+``--cluster-consensus`` (with ``--consensus`` or ``--consensus-levels``) adds
+``consensus_t.../cluster_consensus.tsv`` (``community+1``, size, pair sum, cluster consensus) and
+``consensus_t.../item_consensus.tsv`` (node, ``community+1``, item sum, item consensus with its own
+community), no header, floats as ``%.17g`` (``Engine.cluster_consensus``).
 """
 import argparse
 import os
@@ -61,6 +65,8 @@ def build_parser():
     p.add_argument('--consensus-levels', action='store_true', help=argparse.SUPPRESS)
     # extension: the consensus matrix of K random nodes
     p.add_argument('--coassoc', type=int, default=None, help=argparse.SUPPRESS)
+    # extension: cluster and item consensus of the consensus partition
+    p.add_argument('--cluster-consensus', action='store_true', help=argparse.SUPPRESS)
     return p
 
 
@@ -125,6 +131,22 @@ def write_levels(args, node_labels, levels, labels, root='.'):
                               + [repr(float(r['modularity']))]) + '\n')
 
 
+def write_cluster_consensus(args, node_labels, labels, cc, root='.'):
+    """consensus_t.../cluster_consensus.tsv (community+1, size, pairs, value; one row per community
+    in label order) and /item_consensus.tsv (node label, community+1, item sum, value; one row per
+    node in node order): no header, floats as %.17g.  cc: the dict of Engine.cluster_consensus."""
+    d = os.path.join(root, 'consensus_' + output_dirs(args)[0][len('out_partitions_'):])
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, 'cluster_consensus.tsv'), 'w') as f:
+        for c, n, p, x in zip(cc["ids"].tolist(), cc["size"].tolist(), cc["cluster_pairs"].tolist(),
+                              cc["cluster_consensus"].tolist()):
+            f.write("%d\t%d\t%d\t%.17g\n" % (c + 1, n, p, x))
+    with open(os.path.join(d, 'item_consensus.tsv'), 'w') as f:
+        for v, c, p, x in zip(node_labels.tolist(), labels.tolist(), cc["item_pairs"].tolist(),
+                              cc["item_consensus"].tolist()):
+            f.write("%s\t%d\t%d\t%.17g\n" % (v, c + 1, p, x))
+
+
 def write_coassoc(node_labels, ids, matrix, root='.'):
     """coassoc.npy (int32 [K, K]) and coassoc_nodes.txt (the K node labels, one per line, in the
     matrix's order), beside the output tree."""
@@ -145,7 +167,9 @@ def main(argv=None):
         raise SystemExit("--consensus must lie in [0, 1]")
     if args.consensus is not None and args.consensus_levels:
         raise SystemExit("--consensus and --consensus-levels both write the consensus partition: give one")
-    cons = ca = None
+    if args.cluster_consensus and args.consensus is None and not args.consensus_levels:
+        raise SystemExit("--cluster-consensus needs --consensus or --consensus-levels")
+    cons = ca = cc = None
     g = IdGraph.from_edgelist_file(args.f)
     if args.coassoc is not None and not 0 <= args.coassoc <= g.n:
         raise SystemExit("--coassoc must lie in [0, %d], the number of nodes" % g.n)
@@ -162,6 +186,8 @@ def main(argv=None):
                 cons = eng.consensus_partition(args.consensus)
             if args.consensus_levels:
                 cons = best_consensus(eng)
+            if args.cluster_consensus:
+                cc = eng.cluster_consensus(cons["labels"])
             if args.coassoc is not None:
                 ids = coassoc_nodes(g.n, args.coassoc, g.labels, args.seed)
                 ca = (ids, eng.coassociation(ids).cpu().numpy())
@@ -173,6 +199,8 @@ def main(argv=None):
         write_levels(args, g.labels, cons["levels"], cons["labels"])
     elif cons is not None:
         write_consensus(args, g.labels, cons["labels"])
+    if cc is not None:
+        write_cluster_consensus(args, g.labels, cons["labels"], cc)
     if ca is not None:
         write_coassoc(g.labels, *ca)
 

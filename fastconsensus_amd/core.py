@@ -514,6 +514,84 @@ class Engine:
         (set_timing): ids (upload and map to internal vertices), count (the kernel)."""
         return self._phase_timing(self._L.fc_coassoc_timing, ("ids", "count"))
 
+    # -- cluster and item consensus (fc_cluster_consensus) ----------------------------------
+    def _int64_out(self, dev_out, name):
+        """A contiguous int64 device tensor of at least n elements: `dev_out` when given (checked)."""
+        import torch
+        n = self.n
+        if dev_out is None:
+            return torch.empty(max(n, 1), dtype=torch.int64, device="cuda:%d" % self.device)
+        if dev_out.dtype != torch_int64() or dev_out.numel() < n or not dev_out.is_contiguous():
+            raise ValueError("%s must be a contiguous int64 tensor of >= %d elements" % (name, n))
+        return dev_out
+
+    def cluster_consensus(self, labels, dev_cluster=None, dev_item=None):
+        """Monti et al.'s cluster and item consensus of the partition `labels` ([n] in node order,
+        integer ids in [0, n), not necessarily dense: a consensus cut, one of the replicas, a
+        ground truth) over the local labelings, without the consensus matrix (O(n * n_r)).
+        Returns a dict: ids int32[K] (the distinct ids, ascending) and size int64[K];
+        cluster_pairs int64[K] (the co-association summed over the ordered member pairs of each
+        cluster, diagonal included) and item_pairs int64[n] (each node's co-association summed
+        over the members of its own cluster, itself included); the fc_cluster_info fields (k,
+        max_size, singletons, pairs_total, slow_members, n_r); and cluster_consensus float64[K],
+        item_consensus float64[n], the module-level functions of those integers with n_total =
+        n_r (NaN for a cluster of one node).  `dev_cluster` / `dev_item`: int64 device tensors of
+        >= n elements to write into (pairs of the K clusters, then zeros; item sums in node
+        order); ranks add theirs (SUM), see distributed.cluster_consensus_sharded."""
+        n = self.n
+        labels = np.asarray(labels)
+        if labels.shape != (n,):
+            raise ValueError("the partition must have shape (%d,)" % n)
+        lab = self._node_ids(labels)
+        dev_cluster = self._int64_out(dev_cluster, "dev_cluster")
+        dev_item = self._int64_out(dev_item, "dev_item")
+        ids = np.empty(max(n, 1), np.int32)
+        size = np.empty(max(n, 1), np.int64)
+        info = _lib.ClusterInfo()
+        check(self._L.fc_cluster_consensus(self._ctx, ptr(lab), ptr(ids), ptr(size), self._dev(dev_cluster),
+                                           self._dev(dev_item), ctypes.addressof(info)))
+        k = info.k
+        ids, size = ids[:k].copy(), size[:k].copy()
+        out = {"ids": ids, "size": size, "cluster_pairs": dev_cluster[:k].cpu().numpy(),
+               "item_pairs": dev_item[:n].cpu().numpy()}
+        out.update(info.as_dict())
+        out["cluster_consensus"] = cluster_consensus(out["cluster_pairs"], size, info.n_r)
+        out["item_consensus"] = item_consensus(out["item_pairs"], size[np.searchsorted(ids, lab)], info.n_r)
+        return out
+
+    def cluster_consensus_timing(self):
+        """Device milliseconds of the phases of the last cluster_consensus made with timing on
+        (set_timing): segments, count, fallback."""
+        return self._phase_timing(self._L.fc_cluster_consensus_timing, ("segments", "count", "fallback"))
+
+    def item_consensus(self, nodes, labels, clusters):
+        """int64 [len(nodes), len(clusters)]: entry (i, c) is the co-association of node nodes[i]
+        summed over the members of cluster clusters[c] of the partition `labels` ([n] in node
+        order), the node itself included where it is a member -- the numerator of Monti et al.'s
+        item consensus m_i(k) with any cluster, not only the node's own.  A thin helper over
+        coassociation: its columns are the clusters' members (in chunks, no matrix above 2^26
+        entries), segment-summed on the device with torch.  The cost is co-association's,
+        len(nodes) * (members of the clusters) * n_r: meant for a list of doubtful nodes against a
+        few candidate clusters; cluster_consensus gives every node's own-cluster sum in O(n * n_r)."""
+        import torch
+        nodes = self._node_ids(nodes)
+        labels = np.asarray(labels)
+        if labels.shape != (self.n,):
+            raise ValueError("the partition must have shape (%d,)" % self.n)
+        clusters = np.asarray(clusters).reshape(-1)
+        members = [np.flatnonzero(labels == c).astype(np.int32) for c in clusters]
+        cols = np.concatenate(members) if members else np.zeros(0, np.int32)
+        seg = np.repeat(np.arange(len(members), dtype=np.int64), [len(x) for x in members])
+        if len(nodes) > ITEM_CHUNK:
+            raise ValueError("item_consensus takes at most %d nodes" % ITEM_CHUNK)
+        dev = "cuda:%d" % self.device
+        out = torch.zeros((len(nodes), len(clusters)), dtype=torch.int64, device=dev)
+        width = max(1, ITEM_CHUNK // max(len(nodes), 1))
+        for c0 in range(0, len(cols) if len(nodes) else 0, width):
+            mat = self.coassociation(nodes, cols[c0:c0 + width])
+            out.index_add_(1, torch.as_tensor(seg[c0:c0 + width], device=dev), mat.to(torch.int64))
+        return out.cpu().numpy()
+
     def nmi_matrix(self):
         """Symmetric [n_r, n_r] float64 NMI between the local replicas (unit diagonal)."""
         return self._pair_matrices()[0]
@@ -538,6 +616,40 @@ CONSENSUS_INFO_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.ConsensusInfo
 assert CONSENSUS_INFO_DTYPE.itemsize == ctypes.sizeof(_lib.ConsensusInfo)
 LEVEL_DTYPE = np.dtype([(k, np.dtype(t)) for k, t in _lib.LevelScore._fields_], align=True)
 assert LEVEL_DTYPE.itemsize == ctypes.sizeof(_lib.LevelScore)
+
+
+ITEM_CHUNK = 1 << 26    # Engine.item_consensus: entries of the largest co-association matrix it forms
+
+
+def cluster_consensus(pairs, size, n_total):
+    """Monti et al.'s cluster consensus m(k), float64 [K]: the mean consensus-matrix entry over
+    the pairs i != j of cluster k, (pairs - n_total * size) / (n_total * size * (size - 1)) from
+    the integers of Engine.cluster_consensus (`pairs` counts ordered pairs with the diagonal,
+    which is n_total per node).  NaN where size = 1, as ConsensusClusterPlus gives."""
+    pairs, size = np.asarray(pairs, np.int64), np.asarray(size, np.int64)
+    nt = np.int64(n_total)
+    out = np.full(pairs.shape, np.nan, np.float64)
+    m = size > 1
+    out[m] = (pairs[m] - nt * size[m]) / (nt * size[m] * (size[m] - 1))
+    return out
+
+
+def item_consensus(item, size_of_own, n_total):
+    """Monti et al.'s item consensus m_i(k) of every node with its own cluster, float64 [n]:
+    (item - n_total) / (n_total * (size_of_own - 1)), `size_of_own` the size of each node's
+    cluster.  NaN where that size is 1."""
+    item, size = np.asarray(item, np.int64), np.asarray(size_of_own, np.int64)
+    nt = np.int64(n_total)
+    out = np.full(item.shape, np.nan, np.float64)
+    m = size > 1
+    out[m] = (item[m] - nt) / (nt * (size[m] - 1))
+    return out
+
+
+def cluster_result(eng, labels):
+    """What fast_consensus(cluster_consensus=True) adds to the `consensus` dict."""
+    cc = eng.cluster_consensus(labels)
+    return {k: cc[k] for k in ("cluster_consensus", "item_consensus", "cluster_pairs", "item_pairs")}
 
 
 def level_of(theta, n_total):
@@ -966,7 +1078,7 @@ def relabel_for(algorithm):
 
 def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, seed=None, device=0,
                    return_stats=False, rule="fast_consensus", scores=False, truth=None, consensus=None,
-                   coassoc=None):
+                   coassoc=None, cluster_consensus=False):
     """Drop-in for fast_consensus.py:129 ``fast_consensus(G, algorithm, n_p, thresh, delta)``.
 
     G: an undirected networkx Graph (weights are ignored: the reference resets them to 1,
@@ -1006,7 +1118,15 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     i < j, ``Engine.coassoc_hist``), ``pac`` and ``cdf`` (``pac(hist)``, ``consensus_cdf(hist)``)
     and, with ``consensus`` also given, ``order``: the stable argsort of the nodes by consensus
     label, so that ``matrix[order][:, order]`` is the block heatmap.
+
+    ``cluster_consensus=True`` (needs ``consensus``) adds Monti et al.'s two other summaries of the
+    consensus partition to the ``consensus`` dict (``Engine.cluster_consensus``):
+    ``cluster_consensus`` (float64 per community, in label order: which communities are solid),
+    ``item_consensus`` (float64 per node, with its own community: which nodes are firmly placed)
+    and the exact integers behind them, ``cluster_pairs`` and ``item_pairs``.
     """
+    if cluster_consensus and consensus is None:
+        raise ValueError("cluster_consensus=True needs consensus (a threshold or \"best\")")
     if isinstance(consensus, str) and consensus != "best":
         raise ValueError('consensus must be a threshold in [0, 1] or "best"')
     algo = algo_id(algorithm)
@@ -1035,6 +1155,8 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
             cons = best_consensus(eng)
         else:
             cons = eng.consensus_partition(float(consensus)) if consensus is not None else None
+        if cluster_consensus:   # before consensus_scores replaces the labelings
+            cons.update(cluster_result(eng, cons["labels"]))
         ca = None
         if coassoc is not None:   # before consensus_scores replaces the labelings
             ca = coassoc_result(eng, coassoc_nodes(g.n, coassoc, g.labels, seed), g.labels, cons)

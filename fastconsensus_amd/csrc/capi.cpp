@@ -103,7 +103,7 @@ struct fc_ctx {
     Ctx& c = (ctx)->c;                                           \
     bind(c);
 
-// the fc_*_timing getters: the device time of the last call's phases (Ctx::cp_ms / lv_ms / ca_ms)
+// the fc_*_timing getters: the device time of the last call's phases (Ctx::cp_ms / lv_ms / ca_ms / cc_ms)
 template <int N> static int phase_timing(fc_ctx* ctx, double (Ctx::*src)[N], double* ms) {
     FC_CTX(ctx)
     FC_API_BEGIN
@@ -167,7 +167,8 @@ void fc_destroy(fc_ctx* ctx) {
                       &c.sc_ref, &c.sc_key, &c.sc_val, &c.sc_ulab, &c.sc_cnt, &c.sc_nruns, &c.sc_seg, &c.sc_kd, &c.sc_kp, &c.sc_part, &c.sc_part2, &c.sc_res, &c.sc_want, &c.sc_ovf, &c.sc_e1, &c.sc_e2, &c.sc_fk1, &c.sc_fk2, &c.sc_fcnt, &c.sc_rng,
                       &c.cp_sup, &c.cp_parent, &c.cp_flag, &c.cp_rank, &c.cp_lab, &c.cp_labi, &c.cp_size, &c.cp_hist, &c.cp_nin, &c.cp_nout,
                       &c.lv_birth, &c.lv_up, &c.lv_cursor, &c.lv_bucket, &c.lv_tot, &c.lv_stats, &c.lv_fold, &c.lv_jw,
-                      &c.ca_ids, &c.ca_va, &c.ca_vb, &c.ca_hist};
+                      &c.ca_ids, &c.ca_va, &c.ca_vb, &c.ca_hist,
+                      &c.cc_row, &c.cc_pairs, &c.cc_item, &c.cc_tot, &c.cc_fv1, &c.cc_fv2, &c.cc_fscan};
     for (auto* b : bufs) b->release();
     for (auto e : c.timer.pool) (void)hipEventDestroy(e);
     for (auto e : c.sweep_ev) (void)hipEventDestroy(e);
@@ -615,6 +616,23 @@ int fc_coassoc_hist(fc_ctx* ctx, int64_t k, const int32_t* nodes, int64_t* hist)
 }
 
 int fc_coassoc_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::ca_ms, ms); }
+
+int fc_cluster_consensus(fc_ctx* ctx, const int32_t* labels, int32_t* ids_out, int64_t* size_out, void* dev_cluster,
+                         void* dev_item, fc_cluster_info* info) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    coassoc_state(c);
+    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "cluster consensus handles at most 2048 local replicas");
+    FC_REQUIRE(labels, FC_EINVAL, "null labels");
+    const uint32_t lim = (uint32_t)c.N;
+    for (int64_t i = 0; i < c.N; ++i)
+        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
+                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    cluster_consensus(c, labels, ids_out, size_out, (int64_t*)dev_cluster, (int64_t*)dev_item, info);
+    FC_API_END
+}
+
+int fc_cluster_consensus_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::cc_ms, ms); }
 
 int fc_collect_timing(fc_ctx* ctx, fc_stats* st) {
     FC_CTX(ctx)

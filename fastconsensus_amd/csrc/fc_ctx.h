@@ -99,8 +99,8 @@ struct Timer {
     size_t next = 0;
 };
 
-// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms, written by analysis.h's PhaseMarks)
-constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2;
+// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks)
+constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3;
 
 struct Ctx {
     int device = 0;
@@ -262,6 +262,12 @@ struct Ctx {
     // device time of the last call's phases (timing enabled): ids (upload + map), count
     double ca_ms[CA_PHASES] = {};
     DevBuf ca_ids, ca_va, ca_vb, ca_hist;
+    // cluster and item consensus (cluster.h): the caller's partition in slot order (a buffer of its
+    // own: sc_ref stays the scorer's), pair sums by cluster, item sums by internal vertex, their
+    // total, the fallback's vertex values before and after the sort, the scan of its run lengths
+    // device time of the last call's phases (timing enabled): segments, count, fallback
+    double cc_ms[CC_PHASES] = {};
+    DevBuf cc_row, cc_pairs, cc_item, cc_tot, cc_fv1, cc_fv2, cc_fscan;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = getenv("FC_SCORE_SLOW") ? atoi(getenv("FC_SCORE_SLOW")) : 0;
     // longest community one wave streams; longer ones go to the fallback
@@ -397,6 +403,9 @@ void consensus_cut(Ctx& c, int level, int32_t* labels_out, int64_t* k_out);
 void coassoc_matrix(Ctx& c, int64_t na, const int32_t* a, int64_t nb, const int32_t* b, int32_t* dev_out);
 void coassoc_pairs(Ctx& c, int64_t npairs, const int32_t* pairs, int32_t* dev_out);
 void coassoc_hist(Ctx& c, int64_t k, const int32_t* nodes, int64_t* hist);
+// cluster.h: labels on the host in node order, validated by the caller
+void cluster_consensus(Ctx& c, const int32_t* labels, int32_t* ids_out, int64_t* size_out, int64_t* dev_cluster,
+                       int64_t* dev_item, fc_cluster_info* info);
 // timing helpers
 int timer_begin(Ctx& c);
 void timer_end(Ctx& c, int slot, int begin_ev);

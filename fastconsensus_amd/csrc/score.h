@@ -63,11 +63,11 @@ struct ScStats {
 };
 }  // namespace
 
-// idx: a local replica, or FC_SCORE_REF.  The label row is in slot order and sinv gives each
-// slot's vertex, so the sort reads both in place; one row's buffers serve the next row.
-static ScSeg score_segments(Ctx& c, int idx) {
+// row: a label row in slot order, labels in [0, N) (a local replica, the reference, or cluster.h's
+// partition).  sinv gives each slot's vertex, so the sort reads both in place; one row's buffers
+// serve the next row.
+static ScSeg score_segments(Ctx& c, const int32_t* row) {
     const int64_t N = c.N;
-    const int32_t* row = idx < 0 ? c.sc_ref.as<int32_t>() : c.lab.as<int32_t>() + (int64_t)idx * N;
     uint32_t* k2 = ensure<uint32_t>(c.sc_key, N);
     int32_t* v2 = ensure<int32_t>(c.sc_val, N);
     sort_pairs_public(c, (const uint32_t*)row, k2, (const int32_t*)c.sinv.as<int32_t>(), v2, N, c.key_bits);
@@ -81,6 +81,10 @@ static ScSeg score_segments(Ctx& c, int idx) {
     int32_t* seg = ensure<int32_t>(c.sc_seg, N + 2);
     exclusive_scan(c, (const int32_t*)cnt, seg, k + 1);   // seg[k] = N whatever cnt[k] holds
     return ScSeg{k, seg, v2};
+}
+// idx: a local replica, or FC_SCORE_REF
+static ScSeg score_segments(Ctx& c, int idx) {
+    return score_segments(c, idx < 0 ? c.sc_ref.as<int32_t>() : c.lab.as<int32_t>() + (int64_t)idx * c.N);
 }
 
 // Per block: sum size^2, max size, sum size ln size and (TOT) the 128-bit sum of (community

@@ -187,6 +187,41 @@ def coassoc_hist_sharded(engine, nodes, n_total, device="cuda"):
     return torch.bincount(mat[iu[0], iu[1]].to(torch.int64), minlength=int(n_total) + 1).cpu().numpy()
 
 
+def cluster_consensus_sharded(engine, labels, n_total, device="cuda"):
+    """Engine.cluster_consensus of the partition `labels` over all n_total replicas of a sharded
+    run: each rank sums over ITS local labelings into int64 buffers of one shape (n entries each),
+    one SUM all-reduce per buffer adds them, and every rank normalises the same integers with
+    core.cluster_consensus / core.item_consensus (n_total in place of the local count).  Returns
+    ids, size, cluster_pairs, item_pairs, cluster_consensus, item_consensus and slow_members (the
+    ranks' sum).  A rank without replicas contributes zeros; `labels` is the same on every rank."""
+    from .core import cluster_consensus, item_consensus
+    n = engine.n
+    labels = np.asarray(labels)
+    cuda = "cuda:%d" % engine.device
+    pairs = torch.zeros(max(n, 1), dtype=torch.int64, device=cuda)
+    item = torch.zeros(max(n, 1), dtype=torch.int64, device=cuda)
+    slow = 0
+    if engine.replica_info()[0] > 0:
+        slow = engine.cluster_consensus(labels, dev_cluster=pairs, dev_item=item)["slow_members"]
+    ids, size = np.unique(labels, return_counts=True)
+    slow = torch.tensor([slow], dtype=torch.int64)
+    if not str(device).startswith("cuda"):
+        pairs, item = pairs.cpu(), item.cpu()
+    else:
+        slow = slow.to(cuda)
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(pairs, op=dist.ReduceOp.SUM)
+        dist.all_reduce(item, op=dist.ReduceOp.SUM)
+        dist.all_reduce(slow, op=dist.ReduceOp.SUM)
+    k = len(ids)
+    cp, ip = pairs[:k].cpu().numpy(), item[:n].cpu().numpy()
+    size = size.astype(np.int64)
+    return {"ids": ids.astype(np.int32), "size": size, "cluster_pairs": cp, "item_pairs": ip,
+            "cluster_consensus": cluster_consensus(cp, size, n_total),
+            "item_consensus": item_consensus(ip, size[np.searchsorted(ids, labels)], n_total),
+            "slow_members": int(slow.item()), "n_total": int(n_total)}
+
+
 def _result(res, consensus):
     labels, st = res
     return (labels, st) if consensus is None else (labels, st, st.pop("consensus"))

@@ -403,6 +403,36 @@ int fc_coassoc_hist(fc_ctx* ctx, int64_t k, const int32_t* nodes, int64_t* hist)
  * enabled: ms[2] = ids (upload and map to internal vertices), count (the kernel). */
 int fc_coassoc_timing(fc_ctx* ctx, double* ms);   /* phases of the last call, timing enabled only */
 
+/* ---- cluster and item consensus of a given partition ------------------------------------ */
+/* For a partition P of the nodes (a consensus cut, one of the replicas, a ground truth) and the
+ * local labelings, with coassoc(i, j) = the number of local replicas that put i and j together:
+ *   pairs[k] = sum over the ordered member pairs (i, j) of cluster k, i = j included, of coassoc(i, j)
+ *   item[v]  = sum over the members j of v's own cluster, j = v included, of coassoc(v, j)
+ * computed from the contingency tables between P and every replica, without the matrix: exact
+ * integers in O(n * n_r).  Both are sums over replicas: ranks add theirs (SUM) and normalise by the
+ * total replica count: (pairs - n_total size) / (n_total size (size - 1)) is Monti et al.'s cluster
+ * consensus m(k), (item - n_total) / (n_total (size - 1)) the item consensus m_i(k) of a node with
+ * its own cluster.  Read-only like fc_score_pairs: labelings, reference and random state stay. */
+typedef struct fc_cluster_info {
+    int64_t k, max_size, singletons;
+    int64_t pairs_total;    /* sum_k pairs[k] == sum_v item[v] */
+    int64_t slow_members;   /* (member, replica) pairs the exact fallback handled (diagnostic) */
+    int32_t n_r, pad;
+} fc_cluster_info;
+/* labels: host int32[n] in node order, ids in [0, n), not necessarily dense; the K distinct ids are
+ * reported ascending.  ids_out, size_out: host arrays of capacity n, the first K entries written.
+ * dev_cluster: device int64[n], pairs of the K clusters in that order, then zeros (the same shape on
+ * every rank).  dev_item: device int64[n] in node order.  Any output may be NULL.  All work on the
+ * context's stream; returns after it finished.  FC_ESTATE: no graph or no labelings; FC_EINVAL:
+ * labels NULL or an id outside [0, n) (the message names the index; checked before any launch);
+ * FC_ELIMIT: more than 2048 local replicas.  Nothing is written on error. */
+int fc_cluster_consensus(fc_ctx* ctx, const int32_t* labels, int32_t* ids_out, int64_t* size_out, void* dev_cluster,
+                         void* dev_item, fc_cluster_info* info);
+/* Device time (ms, HIP events) of the phases of the last fc_cluster_consensus made with timing
+ * enabled: ms[3] = segments (upload, sort, run lengths), count (the register-list kernel),
+ * fallback (the exact sort-based path). */
+int fc_cluster_consensus_timing(fc_ctx* ctx, double* ms);
+
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
  * Writes at most m_cap edges into u/v and the planted community of every node. */
