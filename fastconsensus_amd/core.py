@@ -57,6 +57,12 @@ class PinnedHost:
             self.ok = False
 
 
+def device_bytes():
+    """Device bytes currently held by this process's engines through their growable buffers
+    (Engine.close() returns an engine's whole share)."""
+    return int(_lib.load().fc_device_bytes())
+
+
 class Engine:
     """One device-resident consensus engine (one GPU, one host thread)."""
 

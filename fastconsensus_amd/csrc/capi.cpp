@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -20,7 +21,7 @@ int timer_begin(Ctx& c) {
     if (!t.on) return -1;
     if (t.next >= t.pool.size()) {
         size_t add = t.pool.empty() ? 4096 : t.pool.size();
-        for (size_t i = 0; i < add; ++i) {
+        for (t.pool.reserve(t.pool.size() + add); add > 0; --add) {
             hipEvent_t e;
             FC_HIP(hipEventCreate(&e));
             t.pool.push_back(e);
@@ -30,8 +31,7 @@ int timer_begin(Ctx& c) {
     FC_HIP(hipEventRecord(t.pool[idx], c.stream));
     return idx;
 }
-void timer_end(Ctx& c, int slot, int b) { (void)timer_end_ev(c, slot, b); }
-int timer_end_ev(Ctx& c, int slot, int b) {
+int timer_end(Ctx& c, TimerSlot slot, int b) {
     if (b < 0) return -1;
     const int e = timer_begin(c);
     c.timer.spans[slot].push_back({b, e});
@@ -39,10 +39,10 @@ int timer_end_ev(Ctx& c, int slot, int b) {
 }
 void timer_collect(Ctx& c, fc_stats* st) {
     Timer& t = c.timer;
-    double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t launches[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double ms[TS_COUNT] = {};
+    int64_t launches[TS_COUNT] = {};
     if (!t.pool.empty()) FC_HIP(hipStreamSynchronize(c.stream));
-    for (int s = 0; s < 8; ++s) {
+    for (int s = 0; s < TS_COUNT; ++s) {
         for (auto& pr : t.spans[s]) {
             float x = 0.f;
             FC_HIP(hipEventElapsedTime(&x, t.pool[pr.first], t.pool[pr.second]));
@@ -54,11 +54,11 @@ void timer_collect(Ctx& c, fc_stats* st) {
     t.next = 0;
     if (st) {
         *st = c.prof;
-        st->cd_ms = ms[0]; st->consensus_ms = ms[1]; st->closure_ms = ms[2]; st->rebuild_ms = ms[3];
-        st->decide_ms = ms[4]; st->decide_launches = launches[4];
-        st->lv_decide_ms = ms[5]; st->lv_decide_launches = launches[5];
-        st->lv_heavy_ms = ms[6]; st->lv_heavy_launches = launches[6];
-        st->rl_decide_ms = ms[7]; st->rl_decide_launches = launches[7];
+        st->cd_ms = ms[TS_CD]; st->consensus_ms = ms[TS_CONSENSUS]; st->closure_ms = ms[TS_CLOSURE]; st->rebuild_ms = ms[TS_REBUILD];
+        st->decide_ms = ms[TS_DECIDE]; st->decide_launches = launches[TS_DECIDE];
+        st->lv_decide_ms = ms[TS_LV_DECIDE]; st->lv_decide_launches = launches[TS_LV_DECIDE];
+        st->lv_heavy_ms = ms[TS_LV_HEAVY]; st->lv_heavy_launches = launches[TS_LV_HEAVY];
+        st->rl_decide_ms = ms[TS_RL_DECIDE]; st->rl_decide_launches = launches[TS_RL_DECIDE];
     }
     c.prof = fc_stats{};
 }
@@ -133,55 +133,32 @@ int fc_create(int device, uint64_t seed, fc_ctx** out) {
     FC_HIP(hipGetDeviceProperties(&prop, device));
     FC_REQUIRE(std::strstr(prop.gcnArchName, "gfx950") != nullptr, FC_ENODEV,
                std::string("engine is built for gfx950 (MI355X); device is ") + prop.gcnArchName);
-    fc_ctx* x = new fc_ctx();
+    std::unique_ptr<fc_ctx> x(new fc_ctx());   // a failure below frees what the context already owns
     Ctx& c = x->c;
     c.device = device;
     c.seed = seed;
-    try {
-        FC_HIP(hipSetDevice(device));
-        FC_HIP(hipStreamCreateWithFlags(&c.own_stream, hipStreamNonBlocking));
-        c.stream = c.own_stream;
-        FC_HIP(hipHostMalloc((void**)&c.hpin, FC_HPIN_I64 * sizeof(int64_t), hipHostMallocDefault));
-    } catch (...) {
-        delete x;
-        throw;
-    }
-    *out = x;
+    FC_HIP(hipSetDevice(device));
+    FC_HIP(hipStreamCreateWithFlags(&c.own_stream.s, hipStreamNonBlocking));
+    c.stream = c.own_stream.s;
+    FC_HIP(hipHostMalloc((void**)&c.hpin.p, FC_HPIN_I64 * sizeof(int64_t), hipHostMallocDefault));
+    *out = x.release();
     FC_API_END
 }
 
 void fc_destroy(fc_ctx* ctx) {
     if (!ctx) return;
-    Ctx& c = ctx->c;
-    (void)hipSetDevice(c.device);
-    (void)hipStreamSynchronize(c.stream);
-    c.g.release();
-    c.g0.release();
-    DevBuf* bufs[] = {&c.lab, &c.nlab, &c.rl_lmask, &c.rl_vmask, &c.rl_aff, &c.rl_mvf, &c.rl_vlist, &c.rl_vcount, &c.rl_tot, &c.rl_state, &c.rl_colw, &c.rl_slow, &c.rl_slow_cnt, &c.aff_cnt, &c.aff, &c.vlist, &c.vcnt, &c.track, &c.tot, &c.dec, &c.labT, &c.rep_state, &c.heavy_list, &c.heavy_cnt,
-                      &c.heavy_scratch, &c.wnew, &c.flag, &c.pos, &c.ku, &c.kv, &c.kw, &c.kage, &c.krowptr,
-                      &c.kcol, &c.counters, &c.ckey, &c.cval, &c.ckey2, &c.cval2, &c.cu, &c.cv, &c.cw2,
-                      &c.cage, &c.deg_next, &c.iso, &c.isoflag, &c.target, &c.tw, &c.active, &c.active2,
-                      &c.hit, &c.mkey, &c.mkey2, &c.midx, &c.midx2, &c.sort_tmp, &c.nodetmp, &c.nodetmp2,
-                      &c.nodetmp3, &c.part, &c.ccount, &c.tailbuf, &c.tailmark, &c.sigma, &c.npos, &c.spos, &c.sinv, &c.tpos, &c.snpos, &c.st_u, &c.st_v, &c.st_w, &c.st_age,
-                      &c.st_lab, &c.clo_rec, &c.clo_hkey, &c.clo_hval, &c.clo_list, &c.clo_cnt, &c.clo_akey, &c.clo_aval, &c.clo_rowptr, &c.clo_col, &c.clo_rowptr2, &c.clo_col2, &c.clo_nrow, &c.clo_ncol, &c.clo_own, &c.clo_own2, &c.mvf,
-                      &c.sc_ref, &c.sc_key, &c.sc_val, &c.sc_ulab, &c.sc_cnt, &c.sc_nruns, &c.sc_seg, &c.sc_kd, &c.sc_kp, &c.sc_part, &c.sc_part2, &c.sc_res, &c.sc_want, &c.sc_ovf, &c.sc_e1, &c.sc_e2, &c.sc_fk1, &c.sc_fk2, &c.sc_fcnt, &c.sc_rng,
-                      &c.cp_sup, &c.cp_parent, &c.cp_flag, &c.cp_rank, &c.cp_lab, &c.cp_labi, &c.cp_size, &c.cp_hist, &c.cp_nin, &c.cp_nout,
-                      &c.lv_birth, &c.lv_up, &c.lv_cursor, &c.lv_bucket, &c.lv_tot, &c.lv_stats, &c.lv_fold, &c.lv_jw,
-                      &c.ca_ids, &c.ca_va, &c.ca_vb, &c.ca_hist,
-                      &c.cc_row, &c.cc_pairs, &c.cc_item, &c.cc_tot, &c.cc_fv1, &c.cc_fv2, &c.cc_fscan};
-    for (auto* b : bufs) b->release();
-    for (auto e : c.timer.pool) (void)hipEventDestroy(e);
-    for (auto e : c.sweep_ev) (void)hipEventDestroy(e);
-    if (c.hpin) (void)hipHostFree(c.hpin);
-    if (c.own_stream) (void)hipStreamDestroy(c.own_stream);
-    delete ctx;
+    (void)hipSetDevice(ctx->c.device);
+    (void)hipStreamSynchronize(ctx->c.stream);   // in front of every free
+    delete ctx;   // buffers, events, pinned scratch and stream: their owners' destructors
 }
+
+int64_t fc_device_bytes(void) { return DevBuf::held.load(); }
 
 int fc_set_stream(fc_ctx* ctx, void* s) {
     FC_CTX(ctx)
     FC_API_BEGIN
     FC_HIP(hipStreamSynchronize(c.stream));
-    c.stream = s ? (hipStream_t)s : c.own_stream;
+    c.stream = s ? (hipStream_t)s : c.own_stream.s;
     FC_API_END
 }
 

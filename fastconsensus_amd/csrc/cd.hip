@@ -1597,7 +1597,7 @@ struct CdRun {
         // one item per block: X item slots per replica, rounded up to whole XCD groups of 8
         const int64_t grid = (((int64_t)a.n_r * X + 7) / 8) * 8;
         k_decide_light<LOUV, TT><<<(unsigned)grid, DTB, 0, c.stream>>>(a, k, sweep, X);
-        timer_end(c, 4, ev);
+        timer_end(c, TS_DECIDE, ev);
         if (hv) k_decide_heavy<LOUV, TT><<<HEAVY_GRID, TB, 0, c.stream>>>(a, k, sweep);
         // apply: FC_APPLY_BLOCKS blocks per replica, more when few replicas share the GPU (a
         // push/tracking move is a dependent row walk, so the chip needs ~2K resident blocks), but
@@ -1675,7 +1675,7 @@ void cd_run(Ctx& c, int algo, int rbegin, int rcount, int n_p_total, int iterati
         r.end_sweep();
     }
     r.statistics();
-    timer_end(c, 0, sl0);
+    timer_end(c, TS_CD, sl0);
 #ifdef FC_PHASE_PROF
     {
         unsigned long long hp[16];

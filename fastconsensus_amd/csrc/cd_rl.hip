@@ -2003,7 +2003,7 @@ struct RlRun {
             if (n <= 0) return;
             const int ev = timer_begin(c);
             rl_dispatch(louv, [&](auto l) { k_rl_decide_lds<l()><<<rl_grid(rl_items(a, n)), RTB, 0, c.stream>>>(a, k, sweep); });
-            timer_end(c, 7, ev);
+            timer_end(c, TS_RL_DECIDE, ev);
             return;
         }
         // wave mode: a bucket's decide launches follow each other with nothing between them, so the
@@ -2018,7 +2018,7 @@ struct RlRun {
                 rl_dispatch(louv, a.unitw, a.colw, groups.g[gi].K, false, [&](auto l, auto kk, auto w, auto) {
                     k_rl_decide_v<l(), kk(), w()><<<rl_grid((n + 63) / 64), RTB, 0, c.stream>>>(a, seg, ns, sweep);
                 });
-                timer_end(c, 7, ev);
+                timer_end(c, TS_RL_DECIDE, ev);
                 continue;
             }
             rl_dispatch(louv, a.unitw, a.colw, groups.g[gi].K, u1, [&](auto l, auto kk, auto w, auto u) {
@@ -2027,7 +2027,7 @@ struct RlRun {
                     : rl_grid(rl_items(a, n));
                 const int ev = chain_ev >= 0 ? chain_ev : timer_begin(c);
                 k_rl_decide<l(), kk(), w(), u()><<<grid, RTB, 0, c.stream>>>(a, seg, ns, sweep);
-                const int ee = timer_end_ev(c, 7, ev);
+                const int ee = timer_end(c, TS_RL_DECIDE, ev);
                 if (c.timer_chain) chain_ev = ee;
             });
         }
@@ -2114,7 +2114,7 @@ void cd_run_rl(Ctx& c, int algo, int rbegin, int rcount, int n_p_total, int iter
     }
     if (r.handoff < 0) r.export_labels();
     r.statistics();
-    timer_end(c, 0, sl0);
+    timer_end(c, TS_CD, sl0);
     if (r.handoff >= 0) {   // r.a stays alive: rl_handoff_fill reads it through h.user
         if (c.trace) fprintf(stderr, "[fc] rl it=%d hands over to cd.hip at sweep %d\n", iteration, r.handoff);
         const CDHandoff h{r.handoff, rl_handoff_fill, &r.a};

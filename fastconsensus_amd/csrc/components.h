@@ -183,7 +183,7 @@ void consensus_support(Ctx& c, int graph, int32_t* out) {
     ScLabT lt(c);
     const int sl = timer_begin(c);
     launch_pair_partial<false>(c, g.m, g.eu.as<int32_t>(), g.ev.as<int32_t>(), out);
-    timer_end(c, 1, sl);
+    timer_end(c, TS_CONSENSUS, sl);
 }
 
 // The opening of consensus_partition and consensus_levels.  dev_support: null (counted here over the
@@ -271,7 +271,7 @@ void consensus_partition(Ctx& c, int graph, const int32_t* dev_support, int n_to
         }
     }
     ph.mark();   // node sums
-    timer_end(c, 1, sl);
+    timer_end(c, TS_CONSENSUS, sl);
 
     std::vector<unsigned long long> h((size_t)n_total + 2);
     int32_t k = 0;

@@ -87,7 +87,7 @@ void consensus_partial(Ctx& c, int algo, int32_t* out) {
         launch_pair_partial<true>(c, c.g.m, c.g.eu.as<int32_t>(), c.g.ev.as<int32_t>(), out);
     else
         launch_pair_partial<false>(c, c.g.m, c.g.eu.as<int32_t>(), c.g.ev.as<int32_t>(), out);
-    timer_end(c, 1, sl);
+    timer_end(c, TS_CONSENSUS, sl);
 }
 
 // ------------------------------------------------------------------ consensus apply
@@ -202,7 +202,7 @@ void consensus_apply(Ctx& c, int algo, int n_p, double tau, const int32_t* parti
     k_krowptr<<<nblk(c.N + 1), TB, 0, c.stream>>>(c.N, g.rowptr.as<int64_t>(), p2, krowptr);
     if (kept_out) *kept_out = kept;
     if (unconv_out) *unconv_out = unconv;
-    timer_end(c, 1, sl);
+    timer_end(c, TS_CONSENSUS, sl);
 }
 
 // ------------------------------------------------------------------ closure
@@ -571,7 +571,7 @@ void closure_sample(Ctx& c, int64_t attempts, int iteration) {
     }
     // candidates in key order (first-sample ages ride along; the keys are distinct)
     finish_candidates(c, read_i64(c, b.nacc), b.akey, b.aval, iteration);
-    timer_end(c, 2, sl);
+    timer_end(c, TS_CLOSURE, sl);
 }
 
 // ---- the same closure with each block's attempts split over ranks (multi-GPU) ----------------
@@ -605,7 +605,7 @@ int closure_begin(Ctx& c, int64_t attempts, int iteration) {
     c.clo_R = b.R;
     c.clo_next = 0;
     c.clo_iter = iteration;
-    timer_end(c, 2, sl);
+    timer_end(c, TS_CLOSURE, sl);
     return b.R;
 }
 
@@ -625,7 +625,7 @@ int64_t closure_block_sample(Ctx& c, int r, int64_t t_lo, int64_t t_hi, int64_t*
                        " drawn");
         if (count > 0) k_emit_cand<<<nblk(n), TB, 0, c.stream>>>(n, b.slot, b.ps, b.tab, t_lo, out);
     }
-    timer_end(c, 2, sl);
+    timer_end(c, TS_CLOSURE, sl);
     return count;
 }
 
@@ -639,7 +639,7 @@ void closure_block_add(Ctx& c, int r, const int64_t* in, int64_t count) {
         clo_append(c, b, count, t0, r);
     }
     c.clo_next = r + 1;
-    timer_end(c, 2, sl);
+    timer_end(c, TS_CLOSURE, sl);
 }
 
 int64_t closure_finish(Ctx& c) {
@@ -647,7 +647,7 @@ int64_t closure_finish(Ctx& c) {
     const Clo b = clo_bufs(c, c.clo_attempts);
     finish_candidates(c, read_i64(c, b.nacc), b.akey, b.aval, c.clo_iter);
     c.clo_next = -1;
-    timer_end(c, 2, sl);
+    timer_end(c, TS_CLOSURE, sl);
     return c.n_cand;
 }
 
@@ -889,10 +889,10 @@ void closure_apply(Ctx& c, int algo, int n_p, const int32_t* counts, int iterati
                                                                c.cw2.as<int32_t>());
     int64_t nrep = 0;
     if (is_louvain(algo)) nrep = repair(c, iteration);  // lpm has no repair (:260-310)
-    timer_end(c, 2, sl);
+    timer_end(c, TS_CLOSURE, sl);
     sl = timer_begin(c);
     graph_merge_next(c, c.n_cand + nrep);
-    timer_end(c, 3, sl);
+    timer_end(c, TS_REBUILD, sl);
     (void)n_p;
 }
 

@@ -3,8 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <atomic>
 #include <chrono>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/fastconsensus_amd.h"
@@ -46,29 +48,65 @@ struct FcError {
         if (!(cond)) throw ::fc::FcError{(code), (msg)}; \
     } while (0)
 
-// Growable device buffer (never shrinks; grows by 1.5x).
-struct DevBuf {
+// Environment tunables, read when an engine is created: atoi / atoll of the value (a variable set
+// to the empty string gives 0), the default when it is unset; env_flag: set, not empty, not "0..."
+inline int env_int(const char* name, int dflt) { const char* s = getenv(name); return s ? atoi(s) : dflt; }
+inline int64_t env_i64(const char* name, int64_t dflt) { const char* s = getenv(name); return s ? atoll(s) : dflt; }
+inline bool env_flag(const char* name) { const char* s = getenv(name); return s && *s && *s != '0'; }
+
+struct NoCopy {   // what owns a device or runtime resource frees it in its destructor and is never copied
+    NoCopy() = default;
+    NoCopy(const NoCopy&) = delete;
+    NoCopy& operator=(const NoCopy&) = delete;
+};
+
+// Growable device buffer (never shrinks; grows by 1.5x), freed with its owner; move-only.
+struct DevBuf : NoCopy {
     void* p = nullptr;
     size_t bytes = 0;
+    inline static std::atomic<int64_t> held{0};   // bytes of all live buffers (fc_device_bytes): touched when one grows or dies
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }   // both by swap: o leaves with the old block and frees it
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~DevBuf() { release(); }
     template <class T> T* as() const { return static_cast<T*>(p); }
     void ensure(size_t need) {
         if (need <= bytes) return;
         size_t nb = bytes ? bytes + bytes / 2 : 0;
         if (nb < need) nb = need;
         nb = (nb + 255) & ~size_t(255);
-        if (p) {
-            FC_HIP(hipDeviceSynchronize());  // queued kernels may still use the old buffer
-            FC_HIP(hipFree(p));
-        }
-        p = nullptr;
+        if (p) FC_HIP(hipDeviceSynchronize());  // queued kernels may still use the old buffer
+        release();   // p and bytes together: a failed hipMalloc leaves an empty buffer, not a null pointer of the old size
         FC_HIP(hipMalloc(&p, nb));
         bytes = nb;
+        held += (int64_t)nb;
     }
     void release() {
         if (p) (void)hipFree(p);
+        held -= (int64_t)bytes;
         p = nullptr;
         bytes = 0;
     }
+};
+
+// An engine's other raw resources, owned the same way (created by fc_create and timer_begin).
+struct OwnStream : NoCopy {
+    hipStream_t s = nullptr;
+    ~OwnStream() { if (s) (void)hipStreamDestroy(s); }
+};
+struct PinnedI64 : NoCopy {
+    int64_t* p = nullptr;
+    operator int64_t*() const { return p; }
+    ~PinnedI64() { if (p) (void)hipHostFree(p); }
+};
+// timed spans (fc_stats *_ms and *_launches, timer_collect)
+enum TimerSlot { TS_CD, TS_CONSENSUS, TS_CLOSURE, TS_REBUILD, TS_DECIDE, TS_LV_DECIDE, TS_LV_HEAVY, TS_RL_DECIDE, TS_COUNT };
+struct Timer : NoCopy {
+    bool on = false;
+    std::vector<hipEvent_t> pool;
+    std::vector<std::pair<int, int>> spans[TS_COUNT];
+    size_t next = 0;
+    ~Timer() { for (auto e : pool) (void)hipEventDestroy(e); }
 };
 
 // Canonical edge list (u < v in node order, sorted by (u,v)) + symmetric CSR with
@@ -85,28 +123,17 @@ struct Graph {
     int32_t max_deg = 0;
     int64_t max_kdeg = 0;
     int32_t max_w = 0;              // largest edge weight (unit-weight graphs skip the weight loads)
-    void release() {
-        DevBuf* b[] = {&eu, &ev, &ew, &eage, &rowptr, &col, &cw, &ceid, &crev, &colp, &vrec, &kdeg};
-        for (auto* x : b) x->release();
-    }
-};
-
-struct Timer {
-    bool on = false;
-    std::vector<hipEvent_t> pool;
-    // cd, consensus, closure, rebuild, decide, lv decide, lv heavy, rl decide
-    std::vector<std::pair<int, int>> spans[8];
-    size_t next = 0;
 };
 
 // timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks)
 constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3;
 
-struct Ctx {
+// Every resource goes with the member that holds it (fc_destroy synchronises, then deletes).
+struct Ctx : NoCopy {
     int device = 0;
     uint64_t seed = 0;
-    hipStream_t own_stream = nullptr;
-    hipStream_t stream = nullptr;
+    OwnStream own_stream;
+    hipStream_t stream = nullptr;   // own_stream.s, or the caller's (fc_set_stream)
     int64_t N = 0, m_original = 0;
     // internal vertex numbering: internal = sigma[node], node = npos[internal] (a seeded
     // random permutation, or the identity): engine behaviour is independent of input order
@@ -130,18 +157,18 @@ struct Ctx {
     // mover bits [banks][N]; labels and totals node-major in labT / tot ([N][ldT])
     DevBuf rl_lmask, rl_vmask, rl_aff, rl_mvf, rl_vlist, rl_vcount;
     // visit mode for sparse sweeps: when visits * rl_visit_div < entries * min(n_r, 64) (0: never)
-    int rl_visit_div = getenv("FC_RL_VISIT_DIV") ? atoi(getenv("FC_RL_VISIT_DIV")) : 4;
+    int rl_visit_div = env_int("FC_RL_VISIT_DIV", 4);
     // hybrid hand-off into push mode: 0 never, 1 LPA batches (default), 2 every unit-weight batch
-    int rl_handoff_push = getenv("FC_RL_HANDOFF_PUSH") ? atoi(getenv("FC_RL_HANDOFF_PUSH")) : 1;
+    int rl_handoff_push = env_int("FC_RL_HANDOFF_PUSH", 1);
     int cd_engine = 2;              // FC_OPT_CD_ENGINE: 0 classic (cd.hip), 1 replica-lane (cd_rl.hip), 2 hybrid (default)
     // hybrid: the replica-lane engine runs a batch's full sweeps only when it holds this many
     // replicas (8 lanes per vertex at 8: LFR-1M n_p = 8 run 40.3 vs 42.9 ms on cd.hip since the
     // 16-bucket / resident-grid changes; 51.3 vs 46.2 before them)
-    int64_t rl_min_replicas = getenv("FC_RL_MIN_REPLICAS") ? atoll(getenv("FC_RL_MIN_REPLICAS")) : 8;
+    int64_t rl_min_replicas = env_i64("FC_RL_MIN_REPLICAS", 8);
     // ... and the graph this many vertices (a bucket of a smaller graph is too few waves for the
     // replica-lane kernels: LFR-100k louvain 45.9 vs 31.2 ms, LFR-1M 175.8 vs 211 ms; at the
     // round-4 end LFR-100k louvain 33.0 vs 26.5, lpm 24.2 vs 16.6 ms)
-    int64_t rl_min_vertices = getenv("FC_RL_MIN_VERTICES") ? atoll(getenv("FC_RL_MIN_VERTICES")) : 262144;
+    int64_t rl_min_vertices = env_i64("FC_RL_MIN_VERTICES", 262144);
     // hybrid semantics: a filtered sweep visiting >= N/dense_div vertices keeps the shared order
     // (without coarse rounds); 0 = never (FC_OPT_DENSE_DIV).  Measured no gain: LFR-1M 175.9 /
     // 177.7 / 176.7 ms at 0 / 2 / 4, SBM-4M 712 / 759 / 722 ms (profiles/r04_dense_ab.txt)
@@ -159,12 +186,11 @@ struct Ctx {
     DevBuf ku, kv, kw, kage;        // kept canonical list
     DevBuf krowptr, kcol;           // kept CSR (sorted rows)
     DevBuf counters;                // int64 scratch counters
-    DevBuf hcounters;               // (pinned host) mirror
     // closure / repair / merge
     int64_t n_cand = 0;
-    DevBuf ckey, cval, ckey2, cval2;  // uint64 keys + int64 sample index
+    DevBuf ckey, cval, ckey2;       // uint64 keys + int64 sample index
     DevBuf cu, cv, cw2, cage;       // closure edges
-    DevBuf deg_next, iso, isoflag, target, tw, active, active2, hit;
+    DevBuf deg_next, iso, isoflag, target, tw, active, hit;
     int64_t n_iso = 0;
     DevBuf mkey, mkey2, midx, midx2;  // merge sort
     // closure over closure_rounds blocks of attempts (closure_sample): candidate table (uint64
@@ -174,8 +200,8 @@ struct Ctx {
     DevBuf clo_rec;                 // closure: per node {kept row start, length, C row start, length}
     // closure sampler reads the packed node records (0: krowptr / crowptr, the path of graphs past
     // 2^31 entries; FC_CLO_PACK=0 lets the tests run it at small sizes)
-    int clo_pack = getenv("FC_CLO_PACK") ? atoi(getenv("FC_CLO_PACK")) : 1;
-    DevBuf clo_hkey, clo_hval, clo_list, clo_cnt, clo_akey, clo_aval, clo_rowptr, clo_col, clo_rowptr2, clo_col2,
+    int clo_pack = env_int("FC_CLO_PACK", 1);
+    DevBuf clo_hkey, clo_list, clo_cnt, clo_akey, clo_aval, clo_rowptr, clo_col, clo_rowptr2, clo_col2,
         clo_nrow, clo_ncol, clo_own, clo_own2;
     int closure_rounds = 0;         // FC_OPT_CLOSURE_ROUNDS; 0 = per algorithm (closure_blocks below)
     int clo_algo = 0;               // algorithm of the last consensus_apply (the kept graph the closure samples)
@@ -191,53 +217,54 @@ struct Ctx {
     int buckets = 0, max_sweeps = 200, max_iters = 1000;   // buckets 0: cd_buckets' default per algorithm
     int chunk = 16;                 // CD order granularity (0 = per vertex), FC_OPT_CHUNK
     int relabel = 1;                // FC_OPT_RELABEL (applies at the next fc_load_graph)
-    int64_t apply_blocks = getenv("FC_APPLY_BLOCKS") ? atoll(getenv("FC_APPLY_BLOCKS")) : 32;   // per replica
-    std::vector<hipEvent_t> sweep_ev;   // per-sweep completion ring (cd_run)
+    int64_t apply_blocks = env_i64("FC_APPLY_BLOCKS", 32);   // per replica
     DevBuf tailbuf, tailmark;       // CD tail kernel: worklists [n_r][3N], epoch marks [n_r][N]
     // per replica; 0 = off; -1 (default) = per algorithm: 1024 for Louvain (n_p = 8 share 45.5 ->
     // 44.4 ms against 4096), 4096 for LPA (C3 lpm 24.1 -> 22.2 ms against 1024; profiles/r05_tail_ab.txt)
-    int64_t tail_visits = getenv("FC_TAIL_VISITS") ? atoll(getenv("FC_TAIL_VISITS")) : -1;
+    int64_t tail_visits = env_i64("FC_TAIL_VISITS", -1);
     bool order_pass = false;        // store_order()'s CD run (int64 totals, see there)
     int store_order = 1;            // FC_OPT_STORE: label rows in community order (slot spos[v])
-    int order_sweeps = getenv("FC_ORDER_SWEEPS") ? atoi(getenv("FC_ORDER_SWEEPS")) : 3;   // sweeps of that pass (4 until round 6: LFR-1M load -0.37 ms at 3, same run time)
+    int order_sweeps = env_int("FC_ORDER_SWEEPS", 3);   // sweeps of that pass (4 until round 6: LFR-1M load -0.37 ms at 3, same run time)
     // its buckets per sweep: the pass only permutes label storage (results are identical), and
     // 4 big launches per sweep beat 32 small ones (LFR-1M load 9.9 -> 8.0 ms, tools/r03_ordb.sh)
-    int order_buckets = getenv("FC_ORDER_BUCKETS") ? atoi(getenv("FC_ORDER_BUCKETS")) : 4;
+    int order_buckets = env_int("FC_ORDER_BUCKETS", 4);
     DevBuf spos;                    // int32 [N]: storage slot of internal vertex v in every lab row
     int coarsen = 8;                // FC_OPT_COARSEN: 0 off, else the largest g (filtered sweeps in rounds of g buckets)
     double cd_min_dq = 1e-7;        // Louvain sweeps stop below this predicted gain (Leiden's move phase: 0)
     DevBuf lv[64];                  // Leiden level state (leiden.hip)
     int infomap_trials = 10;        // FC_OPT_INFOMAP_TRIALS (igraph community_infomap default)
-    int lv_dense_div = getenv("FC_LV_DENSE_DIV") ? atoi(getenv("FC_LV_DENSE_DIV")) : 0;   // leiden.hip level buckets
+    int lv_dense_div = env_int("FC_LV_DENSE_DIV", 0);   // leiden.hip level buckets
     // leiden.hip aggregate levels: buckets per move sweep (0: B, the level-0 count)
-    int lv_level_b = getenv("FC_LV_LEVEL_B") ? atoi(getenv("FC_LV_LEVEL_B")) : 4;
+    int lv_level_b = env_int("FC_LV_LEVEL_B", 4);
+    bool info_lists = env_int("FC_INFO_LISTS", 1) != 0;   // Infomap passes: compacted bucket lists (0: every bucket launch scans the union)
+    bool lv_g2 = env_int("FC_LV_G2", 1) != 0;   // rows of 65..128 entries: two vertices per wave (256 slots each), not one per wave
     // cd_rl.hip Louvain decide grid: resident waves x rl_grid_mul (0: up to 8192 blocks, as LPA)
-    int rl_grid_mul = getenv("FC_RL_GRID_MUL") ? atoi(getenv("FC_RL_GRID_MUL")) : 1;
+    int rl_grid_mul = env_int("FC_RL_GRID_MUL", 1);
     int prune = 1;                  // FC_OPT_PRUNE: visit only vertices whose neighbour moved (once moves < N/4)
     // CD kernel variant that leaves every decision unchanged (A/B switch, default on):
     // own-label entries summed in registers (ballots / wave scan) instead of the LDS table
-    int own_ballot = getenv("FC_OWN_BALLOT") ? atoi(getenv("FC_OWN_BALLOT")) : 1;
+    int own_ballot = env_int("FC_OWN_BALLOT", 1);
     // sweep-mode thresholds (experiment switches): tracking/pruning after a sweep moving
     // < N/track_div vertices, pull -> push after < N/push_div (0: stay in pull mode)
-    int track_div = getenv("FC_TRACK_DIV") ? atoi(getenv("FC_TRACK_DIV")) : 4;
-    int push_div = getenv("FC_PUSH_DIV") ? atoi(getenv("FC_PUSH_DIV")) : 4;
-    bool trace = getenv("FC_TRACE") && *getenv("FC_TRACE") && *getenv("FC_TRACE") != '0';  // per-sweep stderr
+    int track_div = env_int("FC_TRACK_DIV", 4);
+    int push_div = env_int("FC_PUSH_DIV", 4);
+    bool trace = env_flag("FC_TRACE");   // per-sweep stderr
     Timer timer;
     fc_stats acc{};                 // accumulated during a run (fc_run)
     fc_stats prof{};                // accumulated since the last fc_collect_timing
-    int64_t* hpin = nullptr;        // pinned host scratch (FC_HPIN_I64 int64)
+    PinnedI64 hpin;                 // pinned host scratch (FC_HPIN_I64 int64)
     // cd_rl.hip decide with one unit per wave (64 local replicas or more): the row as one
     // coalesced load an item ahead, neighbour ids by readlane (A/B switch; same decisions)
-    int rl_u1 = getenv("FC_RL_U1") ? atoi(getenv("FC_RL_U1")) : 1;
+    int rl_u1 = env_int("FC_RL_U1", 1);
     // timed decide launches of one bucket share their boundary events (FC_TIMER_CHAIN=0: two each)
-    int timer_chain = getenv("FC_TIMER_CHAIN") ? atoi(getenv("FC_TIMER_CHAIN")) : 1;
+    int timer_chain = env_int("FC_TIMER_CHAIN", 1);
     // replica-lane decide launches per bucket: 3 (networks of 16 / 32 / 64 keys), 4 (+48) or 5
     // (+24 and 48) -- per algorithm (cd_rl.hip, degree classes); 2: one launch for the rows of
     // <= 32 and one for 33..64, each kernel picking the narrower network in the launch: the
     // one-unit-per-wave kernels per row, the per-lane ones by the wave's longest row (FC_RL_SPLIT
     // bits 8 and 16, both set by default; a build without them runs 3 for the per-lane layouts)
-    int rl_groups_louv = getenv("FC_RL_GROUPS_LOUV") ? atoi(getenv("FC_RL_GROUPS_LOUV")) : 2;
-    int rl_groups_lpa = getenv("FC_RL_GROUPS_LPA") ? atoi(getenv("FC_RL_GROUPS_LPA")) : 2;
+    int rl_groups_louv = env_int("FC_RL_GROUPS_LOUV", 2);
+    int rl_groups_lpa = env_int("FC_RL_GROUPS_LPA", 2);
     // partition scoring (score.h): the reference labeling in slot order, one row's sort / segment
     // buffers (reused row after row), per-block partials, fallback masks, offsets and key chunks
     DevBuf sc_ref, sc_key, sc_val, sc_ulab, sc_cnt, sc_nruns, sc_seg, sc_kd, sc_kp, sc_part, sc_part2, sc_res, sc_want,
@@ -269,11 +296,11 @@ struct Ctx {
     double cc_ms[CC_PHASES] = {};
     DevBuf cc_row, cc_pairs, cc_item, cc_tot, cc_fv1, cc_fv2, cc_fscan;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
-    int score_slow = getenv("FC_SCORE_SLOW") ? atoi(getenv("FC_SCORE_SLOW")) : 0;
+    int score_slow = env_int("FC_SCORE_SLOW", 0);
     // longest community one wave streams; longer ones go to the fallback
-    int score_lcap = getenv("FC_SCORE_LCAP") ? atoi(getenv("FC_SCORE_LCAP")) : 16384;
+    int score_lcap = env_int("FC_SCORE_LCAP", 16384);
     // fallback keys per chunk (at least 2 N: an item is up to N keys); 28 bytes of scratch per key
-    int64_t score_chunk = getenv("FC_SCORE_CHUNK") ? atoll(getenv("FC_SCORE_CHUNK")) : (int64_t)1 << 22;
+    int64_t score_chunk = env_i64("FC_SCORE_CHUNK", (int64_t)1 << 22);
 };
 
 constexpr int FC_HPIN_I64 = 2048;   // pinned host scratch: per-sweep records (cd_rl.hip: boff | voff | n_active)
@@ -408,8 +435,7 @@ void cluster_consensus(Ctx& c, const int32_t* labels, int32_t* ids_out, int64_t*
                        int64_t* dev_item, fc_cluster_info* info);
 // timing helpers
 int timer_begin(Ctx& c);
-void timer_end(Ctx& c, int slot, int begin_ev);
-int timer_end_ev(Ctx& c, int slot, int begin_ev);   // timer_end, returning the end event (-1: off)
+int timer_end(Ctx& c, TimerSlot slot, int begin_ev);   // returns the end event (-1: off)
 void timer_collect(Ctx& c, fc_stats* st);
 // scratch helpers
 template <class T> inline T* ensure(DevBuf& b, size_t count) {

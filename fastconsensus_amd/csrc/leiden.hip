@@ -1407,17 +1407,13 @@ struct LvRun {
 
     // one bucketed sweep; returns moves
     unsigned long long sweep(int mode, int level, int sw) {
-        // Infomap passes: compacted bucket lists (FC_INFO_LISTS=0: every bucket launch scans the union)
-        static const bool info_lists = !getenv("FC_INFO_LISTS") || atoi(getenv("FC_INFO_LISTS")) != 0;
-        // rows of 65..128 entries: two vertices per wave (256 slots each), not one per wave
-        static const bool lv_g2 = !getenv("FC_LV_G2") || atoi(getenv("FC_LV_G2")) != 0;
         set_keys(level, sw, (uint32_t)mode);
         FC_HIP(hipMemsetAsync(moves, 0, 8 * MSH, c.stream));
         int nblk = a.bmap ? a.bpr * a.nact : (int)nb(nU);
         const int hg = heavy_grid(a.hslots);
         const int hblk = 64;
         // Infomap: the pass's bucket lists (one host read of the B counts per pass)
-        const bool listed = mode == MODE_INFO && info_lists && a.B <= ILIST_MAXB;
+        const bool listed = mode == MODE_INFO && c.info_lists && a.B <= ILIST_MAXB;
         int32_t* ill = nullptr;
         a.ilist = nullptr;
         if (listed) {
@@ -1453,18 +1449,18 @@ struct LvRun {
             dispatch(impl, mode, [&](auto im, auto md) {
                 constexpr bool IM = im();
                 constexpr int MD = md();
-                // (timed per launch into spans 5 / 6 when timing is on: lv decide / lv heavy)
+                // (timed per launch into TS_LV_DECIDE / TS_LV_HEAVY when timing is on)
                 const int t5 = timer_begin(c);
                 if (max_deg <= 64) k_lv_decide<IM, MD, 512, 4><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);
-                else if (max_deg <= 128 && lv_g2) k_lv_decide<IM, MD, 512, 2><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);
+                else if (max_deg <= 128 && c.lv_g2) k_lv_decide<IM, MD, 512, 2><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);
                 else if (max_deg <= LWS_SMALL / 2) k_lv_decide<IM, MD, LWS_SMALL, 1><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);
                 else k_lv_decide<IM, MD, LWS, 1><<<nblk, LTB, 0, c.stream>>>(a, b, stamp);
-                timer_end(c, 5, t5);
+                timer_end(c, TS_LV_DECIDE, t5);
                 if (max_deg > LIGHT)   // one timer span per kernel launch, as rocprofv3 counts them
                     for_heavy_tiers(max_deg, hg, [&](auto hs, int grid, int tier) {
                         const int t6 = timer_begin(c);
                         k_lv_heavy<IM, MD, hs()><<<grid, LTB, 0, c.stream>>>(a, stamp, tier);
-                        timer_end(c, 6, t6);
+                        timer_end(c, TS_LV_HEAVY, t6);
                     });
                 k_lv_apply<IM, MD><<<nblk + (max_deg > LIGHT ? hblk : 0), LTB, 0, c.stream>>>(a, nblk, hblk, stamp);
             });
@@ -1790,7 +1786,7 @@ static void multilevel(Ctx& c, bool info, int rbegin, int rcount, int n_p_total,
     run.statistics(level + 1, cl_out);
     c.n_r = rcount; c.rbase = rbegin; c.n_p_total = n_p_total;
     c.labT_valid = false;
-    timer_end(c, 0, sl0);
+    timer_end(c, TS_CD, sl0);
     sync(c);
 }
 

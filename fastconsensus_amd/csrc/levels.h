@@ -270,7 +270,7 @@ void consensus_levels(Ctx& c, int graph, const int32_t* dev_support, int n_total
     FC_HIP(hipMemcpyAsync(h.data(), hist, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost, c.stream));
     sync(c);   // the host skips the empty levels
     if (h[(size_t)nt + 1] != 0) {
-        timer_end(c, 1, sl);
+        timer_end(c, TS_CONSENSUS, sl);
         FC_REQUIRE(false, FC_EINVAL, std::to_string(h[(size_t)nt + 1]) + " support values outside [0, n_total]");
     }
     ph.mark();   // bucket
@@ -315,7 +315,7 @@ void consensus_levels(Ctx& c, int graph, const int32_t* dev_support, int n_total
     std::vector<unsigned long long> hj((size_t)nt + 1);
     FC_HIP(hipMemcpyAsync(hj.data(), jw, sizeof(uint64_t) * hj.size(), hipMemcpyDeviceToHost, c.stream));
     ph.mark();   // join levels
-    timer_end(c, 1, sl);
+    timer_end(c, TS_CONSENSUS, sl);
     sync(c);
     ph.collect();
     c.lv_valid = true;
@@ -369,7 +369,7 @@ void consensus_cut(Ctx& c, int level, int32_t* labels_out, int64_t* k_out) {
     k_lv_cut<<<nblk(N + 1), TB, 0, c.stream>>>(N, level, c.lv_birth.as<int32_t>(), c.lv_up.as<int32_t>(), root, flag);
     exclusive_scan(c, (const int32_t*)flag, rank, N + 1);   // rank[N] = k
     k_lv_label<<<nblk(N), TB, 0, c.stream>>>(N, root, rank, lab);
-    timer_end(c, 1, sl);
+    timer_end(c, TS_CONSENSUS, sl);
     int32_t k = 0;
     FC_HIP(hipMemcpyAsync(&k, rank + N, sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
     sync(c);

@@ -77,7 +77,7 @@ static ScSeg score_segments(Ctx& c, const int32_t* row) {
     run_length(c, (const uint32_t*)k2, ul, cnt, nr, N);
     FC_HIP(hipMemcpyAsync(c.hpin, nr, sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
     sync(c);
-    const int64_t k = *(const int32_t*)c.hpin;
+    const int64_t k = *(const int32_t*)c.hpin.p;
     int32_t* seg = ensure<int32_t>(c.sc_seg, N + 2);
     exclusive_scan(c, (const int32_t*)cnt, seg, k + 1);   // seg[k] = N whatever cnt[k] holds
     return ScSeg{k, seg, v2};

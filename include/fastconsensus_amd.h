@@ -98,6 +98,9 @@ const char* fc_build_hash(void);
 /* device: HIP ordinal; seed: drives every random choice (CD order/ties, closure). */
 int fc_create(int device, uint64_t seed, fc_ctx** out);
 void fc_destroy(fc_ctx* ctx);
+/* Device bytes currently held by this process's engines through their growable buffers
+ * (fc_destroy returns a context's whole share). */
+int64_t fc_device_bytes(void);
 /* Run all work on an external stream (e.g. torch.cuda.current_stream().cuda_stream).
  * NULL restores the context's own stream. */
 int fc_set_stream(fc_ctx* ctx, void* hip_stream);
