@@ -18,6 +18,15 @@
  *   - Host arrays are caller-owned and copied; device buffers are context-owned, except
  *     buffers passed as `void* dev_*` which the caller owns (e.g. torch tensors used as
  *     RCCL all-reduce buffers).
+ *   - A context is long-lived and may be used again and again.  A result depends on the seed,
+ *     the options in force, the loaded graph (with the working graph and the labelings the
+ *     calls since fc_load_graph left) and the call's arguments -- and on nothing else the
+ *     context did before: not on earlier graphs, replica counts, algorithms, CD engines,
+ *     failed or abandoned calls, nor on timing being on (tests/test_gpu_engine_reuse.py).
+ *     The documented exceptions: FC_OPT_RELABEL, FC_OPT_STORE and FC_OPT_SEED apply at the
+ *     next fc_load_graph; fc_consensus_cut reads the hierarchy of the last
+ *     fc_consensus_levels, kept until the next fc_load_graph; fc_load_graph drops the
+ *     reference labeling of fc_score_set_reference and the labelings.
  */
 #ifndef FASTCONSENSUS_AMD_H
 #define FASTCONSENSUS_AMD_H

@@ -54,48 +54,54 @@ def dev_i32(n):
     return torch.zeros(max(int(n), 1), dtype=torch.int32, device="cuda")
 
 
+def run_infomap(eng, case):
+    """Loads the case's graph into `eng` (whose seed is case.seed) and runs it.  Returns (labels,
+    renumbered labels, stats of the Infomap run alone, the working graph (n, u, v, w) the run saw,
+    the engine's node map)."""
+    if case.buckets:
+        eng.set_params(buckets=case.buckets)
+    eng.set_option("infomap_trials", case.trials)
+    if case.relabel != 1:
+        eng.set_option("relabel", case.relabel)
+    if case.graph == "lfr1k_consensus":
+        # one lpm-style consensus step of the step API: co-membership weights, weight-0 closure edges
+        gc = golden_io.load("lfr1k_lpm_np20")
+        n, e = gc.N, gc.edges_file
+        eng.load_graph(n, e[:, 0], e[:, 1])
+        eng.cd(1, 0, CONSENSUS_NP, CONSENSUS_NP, 0)
+        part = dev_i32(eng.m)
+        eng.consensus_partial(1, part)
+        eng.consensus_apply(1, CONSENSUS_NP, gc.tau, gc.delta, part)
+        cnt = dev_i32(eng.closure_set_pairs(gc.pair_batches[0], 0))
+        eng.closure_partial(cnt)
+        eng.closure_apply(1, CONSENSUS_NP, gc.delta, cnt, 0)
+    elif case.graph == "lfr1k_weighted":
+        # one Louvain iteration of the step API, as tests/test_gpu_leiden_twin.py builds it
+        gc = golden_io.load("lfr1k_louvain_np20")
+        n, e = gc.N, gc.edges_file
+        eng.load_graph(n, e[:, 0], e[:, 1])
+        eng.cd(0, 0, WEIGHTED_NP, WEIGHTED_NP, 0)
+        part = dev_i32(eng.m)
+        eng.consensus_partial(0, part)
+        eng.consensus_apply(0, WEIGHTED_NP, gc.tau, gc.delta, part)
+        cnt = dev_i32(eng.closure_set_pairs(gc.pair_batches[0], 0))
+        eng.closure_partial(cnt)
+        eng.closure_apply(0, WEIGHTED_NP, gc.delta, cnt, 0)
+    else:
+        n, e = case.edges()
+        eng.load_graph(n, e[:, 0], e[:, 1])
+    u, v, w, _ = eng.get_graph()
+    eng.collect_timing()                                   # counters from here on: the Infomap run's
+    eng.cd(4, case.rbegin, case.count, case.total, case.iteration)
+    lab = eng.get_labels(case.count)
+    ren = eng.get_labels(case.count, renumber=True)
+    return lab, ren, eng.collect_timing(), (n, u, v, w), eng.node_map()
+
+
 def device_infomap(fc, case):
-    """Runs the case on the device.  Returns (labels, renumbered labels, stats of the Infomap run
-    alone, the working graph (n, u, v, w) the run saw, the engine's node map)."""
+    """Runs the case on a new engine (run_infomap)."""
     with fc.Engine(seed=case.seed) as eng:
-        if case.buckets:
-            eng.set_params(buckets=case.buckets)
-        eng.set_option("infomap_trials", case.trials)
-        if case.relabel != 1:
-            eng.set_option("relabel", case.relabel)
-        if case.graph == "lfr1k_consensus":
-            # one lpm-style consensus step of the step API: co-membership weights, weight-0 closure edges
-            gc = golden_io.load("lfr1k_lpm_np20")
-            n, e = gc.N, gc.edges_file
-            eng.load_graph(n, e[:, 0], e[:, 1])
-            eng.cd(1, 0, CONSENSUS_NP, CONSENSUS_NP, 0)
-            part = dev_i32(eng.m)
-            eng.consensus_partial(1, part)
-            eng.consensus_apply(1, CONSENSUS_NP, gc.tau, gc.delta, part)
-            cnt = dev_i32(eng.closure_set_pairs(gc.pair_batches[0], 0))
-            eng.closure_partial(cnt)
-            eng.closure_apply(1, CONSENSUS_NP, gc.delta, cnt, 0)
-        elif case.graph == "lfr1k_weighted":
-            # one Louvain iteration of the step API, as tests/test_gpu_leiden_twin.py builds it
-            gc = golden_io.load("lfr1k_louvain_np20")
-            n, e = gc.N, gc.edges_file
-            eng.load_graph(n, e[:, 0], e[:, 1])
-            eng.cd(0, 0, WEIGHTED_NP, WEIGHTED_NP, 0)
-            part = dev_i32(eng.m)
-            eng.consensus_partial(0, part)
-            eng.consensus_apply(0, WEIGHTED_NP, gc.tau, gc.delta, part)
-            cnt = dev_i32(eng.closure_set_pairs(gc.pair_batches[0], 0))
-            eng.closure_partial(cnt)
-            eng.closure_apply(0, WEIGHTED_NP, gc.delta, cnt, 0)
-        else:
-            n, e = case.edges()
-            eng.load_graph(n, e[:, 0], e[:, 1])
-        u, v, w, _ = eng.get_graph()
-        eng.collect_timing()                                   # counters from here on: the Infomap run's
-        eng.cd(4, case.rbegin, case.count, case.total, case.iteration)
-        lab = eng.get_labels(case.count)
-        ren = eng.get_labels(case.count, renumber=True)
-        return lab, ren, eng.collect_timing(), (n, u, v, w), eng.node_map()
+        return run_infomap(eng, case)
 
 
 def check_case(case, lab, ren, st, graph, sigma):

@@ -42,33 +42,39 @@ def dev_i32(n):
     return torch.zeros(max(int(n), 1), dtype=torch.int32, device="cuda")
 
 
+def run_leiden(eng, case):
+    """Loads the case's graph into `eng` (whose seed is case.seed) and runs it.  Returns (labels,
+    renumbered labels, stats of the Leiden run alone, the working graph (n, u, v, w) the run saw,
+    the engine's node map)."""
+    if case.buckets:
+        eng.set_params(buckets=case.buckets)
+    if case.graph == "lfr1k_weighted":
+        # one Louvain iteration of the step API: consensus weights up to WEIGHTED_NP
+        gc = golden_io.load("lfr1k_louvain_np20")
+        n, e = gc.N, gc.edges_file
+        eng.load_graph(n, e[:, 0], e[:, 1])
+        eng.cd(0, 0, WEIGHTED_NP, WEIGHTED_NP, 0)
+        part = dev_i32(eng.m)
+        eng.consensus_partial(0, part)
+        eng.consensus_apply(0, WEIGHTED_NP, gc.tau, gc.delta, part)
+        cnt = dev_i32(eng.closure_set_pairs(gc.pair_batches[0], 0))
+        eng.closure_partial(cnt)
+        eng.closure_apply(0, WEIGHTED_NP, gc.delta, cnt, 0)
+    else:
+        n, e = case.edges()
+        eng.load_graph(n, e[:, 0], e[:, 1])
+    u, v, w, _ = eng.get_graph()
+    eng.collect_timing()                                   # counters from here on: the Leiden run's
+    eng.cd(3, case.rbegin, case.count, case.total, case.iteration)
+    lab = eng.get_labels(case.count)
+    ren = eng.get_labels(case.count, renumber=True)
+    return lab, ren, eng.collect_timing(), (n, u, v, w), eng.node_map()
+
+
 def device_leiden(fc, case):
-    """Runs the case on the device.  Returns (labels, renumbered labels, stats of the Leiden run
-    alone, the working graph (n, u, v, w) the run saw, the engine's node map)."""
+    """Runs the case on a new engine (run_leiden)."""
     with fc.Engine(seed=case.seed) as eng:
-        if case.buckets:
-            eng.set_params(buckets=case.buckets)
-        if case.graph == "lfr1k_weighted":
-            # one Louvain iteration of the step API: consensus weights up to WEIGHTED_NP
-            gc = golden_io.load("lfr1k_louvain_np20")
-            n, e = gc.N, gc.edges_file
-            eng.load_graph(n, e[:, 0], e[:, 1])
-            eng.cd(0, 0, WEIGHTED_NP, WEIGHTED_NP, 0)
-            part = dev_i32(eng.m)
-            eng.consensus_partial(0, part)
-            eng.consensus_apply(0, WEIGHTED_NP, gc.tau, gc.delta, part)
-            cnt = dev_i32(eng.closure_set_pairs(gc.pair_batches[0], 0))
-            eng.closure_partial(cnt)
-            eng.closure_apply(0, WEIGHTED_NP, gc.delta, cnt, 0)
-        else:
-            n, e = case.edges()
-            eng.load_graph(n, e[:, 0], e[:, 1])
-        u, v, w, _ = eng.get_graph()
-        eng.collect_timing()                                   # counters from here on: the Leiden run's
-        eng.cd(3, case.rbegin, case.count, case.total, case.iteration)
-        lab = eng.get_labels(case.count)
-        ren = eng.get_labels(case.count, renumber=True)
-        return lab, ren, eng.collect_timing(), (n, u, v, w), eng.node_map()
+        return run_leiden(eng, case)
 
 
 def check_case(case, lab, ren, st, graph, sigma):

@@ -7,7 +7,7 @@ import pytest
 
 from oracle import oracle as orc
 from tests import golden_io
-from tests.twin_graph import internal_graph
+from tests.twin_graph import cd_twin, internal_graph
 
 pytestmark = pytest.mark.gpu
 
@@ -170,11 +170,7 @@ def test_consensus_second_iteration_weights(fcmod):
 def _twin(eng, algo, N, e, count, r0, iteration, seed, **kw):
     """The CPU twin on the engine's internal numbering (fc_get_node_map), labels returned
     in node order like fc_get_labels."""
-    sigma = eng.node_map()
-    assert np.array_equal(np.sort(sigma), np.arange(N))
-    g_int = orc.EdgeGraph.from_lines(N, np.stack([sigma[e[:, 0]], sigma[e[:, 1]]], 1))
-    lab, sw = orc.engine_cd(algo, g_int, count, r0, iteration, seed, **kw)
-    return lab[:, sigma], sw
+    return cd_twin(eng.node_map(), algo, N, e, count, r0, iteration, seed, **kw)
 
 
 @pytest.mark.parametrize("n,seed", [(1000, 100), (1000, 259), (34, 7), (1_000_003, 42)])
