@@ -35,6 +35,7 @@ SYMBOLS = [
     "fc_consensus_levels", "fc_consensus_cut", "fc_consensus_levels_timing",
     "fc_coassociation", "fc_coassoc_pairs", "fc_coassoc_hist", "fc_coassoc_timing",
     "fc_cluster_consensus", "fc_cluster_consensus_timing",
+    "fc_vote_map", "fc_vote_count", "fc_vote", "fc_vote_timing",
 ]
 FC_SCORE_REF = -1
 SCORE_GRAPHS = {"input": 0, "working": 1}
@@ -115,6 +116,19 @@ class ClusterInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class VoteInfo(ctypes.Structure):
+    """fc_vote_info"""
+    _fields_ = [
+        ("k", ctypes.c_int64), ("k_voted", ctypes.c_int64), ("moved", ctypes.c_int64),
+        ("unanimous", ctypes.c_int64), ("tied", ctypes.c_int64), ("mapped_communities", ctypes.c_int64),
+        ("slow_members", ctypes.c_int64), ("slow_nodes", ctypes.c_int64), ("n_total", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 _lib = None
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
@@ -187,6 +201,11 @@ def load():
     # labels (host), ids_out, size_out (host or NULL), dev_cluster, dev_item (device or NULL), fc_cluster_info
     L.fc_cluster_consensus.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.fc_cluster_consensus_timing.argtypes = [vp, P(dbl)]
+    L.fc_vote_map.argtypes = [vp, vp, vp, vp]              # labels (host), dev_mapped, fc_vote_info
+    # labels (host), dev_mapped, n_total, dev_top, dev_top_votes, dev_own_votes, own_hist (host), fc_vote_info
+    L.fc_vote_count.argtypes = [vp, vp, vp, c_int, vp, vp, vp, vp, vp]
+    L.fc_vote.argtypes = [vp, vp, vp, vp, vp, vp, vp]      # the same without dev_mapped and n_total
+    L.fc_vote_timing.argtypes = [vp, P(dbl)]
     _lib = L
     return L
 

@@ -15,6 +15,9 @@ of K nodes drawn by ``numpy.random.default_rng(seed)``, ``Engine.coassociation``
 ``consensus_t.../cluster_consensus.tsv`` (``community+1``, size, pair sum, cluster consensus) and
 ``consensus_t.../item_consensus.tsv`` (node, ``community+1``, item sum, item consensus with its own
 community), no header, floats as ``%.17g`` (``Engine.cluster_consensus``).
+``--vote`` (with ``--consensus`` or ``--consensus-levels``) votes on the consensus partition
+(``Engine.vote``) and adds ``consensus_t.../vote.tsv``: node, ``community+1``, voted
+``community+1``, own votes, top votes; one row per node in node order, no header.
 """
 import argparse
 import os
@@ -67,6 +70,8 @@ def build_parser():
     p.add_argument('--coassoc', type=int, default=None, help=argparse.SUPPRESS)
     # extension: cluster and item consensus of the consensus partition
     p.add_argument('--cluster-consensus', action='store_true', help=argparse.SUPPRESS)
+    # extension: plurality vote of the partitions on the consensus partition
+    p.add_argument('--vote', action='store_true', help=argparse.SUPPRESS)
     return p
 
 
@@ -147,6 +152,17 @@ def write_cluster_consensus(args, node_labels, labels, cc, root='.'):
             f.write("%s\t%d\t%d\t%.17g\n" % (v, c + 1, p, x))
 
 
+def write_vote(args, node_labels, labels, vt, root='.'):
+    """consensus_t.../vote.tsv (node label, community+1, voted community+1, own votes, top votes;
+    one row per node in node order, no header).  vt: the dict of Engine.vote on `labels`."""
+    d = os.path.join(root, 'consensus_' + output_dirs(args)[0][len('out_partitions_'):])
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, 'vote.tsv'), 'w') as f:
+        for v, c, t, o, tv in zip(node_labels.tolist(), labels.tolist(), vt["top"].tolist(), vt["own_votes"].tolist(),
+                                  vt["top_votes"].tolist()):
+            f.write("%s\t%d\t%d\t%d\t%d\n" % (v, c + 1, t + 1, o, tv))
+
+
 def write_coassoc(node_labels, ids, matrix, root='.'):
     """coassoc.npy (int32 [K, K]) and coassoc_nodes.txt (the K node labels, one per line, in the
     matrix's order), beside the output tree."""
@@ -169,7 +185,9 @@ def main(argv=None):
         raise SystemExit("--consensus and --consensus-levels both write the consensus partition: give one")
     if args.cluster_consensus and args.consensus is None and not args.consensus_levels:
         raise SystemExit("--cluster-consensus needs --consensus or --consensus-levels")
-    cons = ca = cc = None
+    if args.vote and args.consensus is None and not args.consensus_levels:
+        raise SystemExit("--vote needs --consensus or --consensus-levels")
+    cons = ca = cc = vt = None
     g = IdGraph.from_edgelist_file(args.f)
     if args.coassoc is not None and not 0 <= args.coassoc <= g.n:
         raise SystemExit("--coassoc must lie in [0, %d], the number of nodes" % g.n)
@@ -188,6 +206,8 @@ def main(argv=None):
                 cons = best_consensus(eng)
             if args.cluster_consensus:
                 cc = eng.cluster_consensus(cons["labels"])
+            if args.vote:
+                vt = eng.vote(cons["labels"])
             if args.coassoc is not None:
                 ids = coassoc_nodes(g.n, args.coassoc, g.labels, args.seed)
                 ca = (ids, eng.coassociation(ids).cpu().numpy())
@@ -201,6 +221,8 @@ def main(argv=None):
         write_consensus(args, g.labels, cons["labels"])
     if cc is not None:
         write_cluster_consensus(args, g.labels, cons["labels"], cc)
+    if vt is not None:
+        write_vote(args, g.labels, cons["labels"], vt)
     if ca is not None:
         write_coassoc(g.labels, *ca)
 

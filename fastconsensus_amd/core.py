@@ -570,6 +570,72 @@ class Engine:
         (set_timing): segments, count, fallback."""
         return self._phase_timing(self._L.fc_cluster_consensus_timing, ("segments", "count", "fallback"))
 
+    # -- plurality vote (fc_vote_map / fc_vote_count / fc_vote) ----------------------------
+    def _vote_labels(self, labels):
+        labels = np.asarray(labels)
+        if labels.shape != (self.n,):
+            raise ValueError("the partition must have shape (%d,)" % self.n)
+        return self._node_ids(labels)
+
+    def vote_map(self, labels, dev_mapped=None):
+        """Every local labeling relabelled onto the partition `labels` ([n] in node order, ids in
+        [0, n), not necessarily dense): each community of replica r becomes the cluster of
+        `labels` it shares the most nodes with (the smallest id among equals).  Returns a dict:
+        mapped (an int32 device tensor [n_r, n], replica-major, node order, values are ids of
+        `labels`; written into `dev_mapped`, contiguous int32 of >= n_r * n elements, when given)
+        and k, mapped_communities, slow_members, n_total (= n_r) of fc_vote_info.  Only this
+        depends on which rank holds a replica: distributed.vote_sharded all-gathers it."""
+        lab = self._vote_labels(labels)
+        n_r, n = self.replica_info()[0], self.n
+        out = self._int32_out(dev_mapped, n_r * n, contiguous=True)
+        info = _lib.VoteInfo()
+        check(self._L.fc_vote_map(self._ctx, ptr(lab), self._dev(out), ctypes.addressof(info)))
+        self._written()
+        d = info.as_dict()
+        res = {k: d[k] for k in ("k", "mapped_communities", "slow_members", "n_total")}
+        res["mapped"] = out.reshape(-1)[:n_r * n].view(n_r, n)
+        return res
+
+    def vote(self, labels, dev_mapped=None, n_total=None):
+        """Plurality vote of the labelings on the partition `labels` (relabel-and-vote): every
+        replica votes, per node, for the cluster its community of that node maps to (vote_map).
+        Returns a dict: top int32[n] (the cluster of most votes: the node's own when it is among
+        several, else the smallest id), top_votes and own_votes int32[n] (the votes for `top` and
+        for the node's own cluster), confidence float64[n] = own_votes / n_total ("x of n_total
+        runs agree"), own_hist int64[n_total + 1] and the fc_vote_info fields (k, k_voted, moved,
+        unanimous, tied, mapped_communities, slow_members, slow_nodes, n_total).
+        `dev_mapped`: None (the local labelings are mapped, n_total = their number) or an int32
+        device tensor [n_total, n] of vote_map's layout, from this engine or gathered over ranks;
+        no labelings are needed then, and the map's three fields are 0."""
+        lab = self._vote_labels(labels)
+        n = self.n
+        if dev_mapped is None:
+            nt = self.replica_info()[0]
+        else:
+            nt = int(dev_mapped.shape[0] if n_total is None else n_total)
+            if dev_mapped.dtype != torch_int32() or not dev_mapped.is_contiguous() or dev_mapped.numel() < nt * n:
+                raise ValueError("dev_mapped must be a contiguous int32 tensor of >= n_total * n elements")
+        top, tv, own = (self._int32_out(None, n) for _ in range(3))
+        hist = np.zeros(max(nt, 0) + 1, np.int64)
+        info = _lib.VoteInfo()
+        if dev_mapped is None:
+            check(self._L.fc_vote(self._ctx, ptr(lab), self._dev(top), self._dev(tv), self._dev(own), ptr(hist),
+                                  ctypes.addressof(info)))
+        else:
+            check(self._L.fc_vote_count(self._ctx, ptr(lab), self._dev(dev_mapped), nt, self._dev(top), self._dev(tv),
+                                        self._dev(own), ptr(hist), ctypes.addressof(info)))
+        self._written()
+        out = info.as_dict()
+        out.update(top=top[:n].cpu().numpy(), top_votes=tv[:n].cpu().numpy(), own_votes=own[:n].cpu().numpy(),
+                   own_hist=hist)
+        out["confidence"] = out["own_votes"].astype(np.float64) / np.float64(out["n_total"])
+        return out
+
+    def vote_timing(self):
+        """Device milliseconds of the phases of the last vote / vote_map made with timing on
+        (set_timing): segments, map, map_fallback, count (0.0 for a phase the call did not run)."""
+        return self._phase_timing(self._L.fc_vote_timing, ("segments", "map", "map_fallback", "count"))
+
     def item_consensus(self, nodes, labels, clusters):
         """int64 [len(nodes), len(clusters)]: entry (i, c) is the co-association of node nodes[i]
         summed over the members of cluster clusters[c] of the partition `labels` ([n] in node
@@ -656,6 +722,34 @@ def cluster_result(eng, labels):
     """What fast_consensus(cluster_consensus=True) adds to the `consensus` dict."""
     cc = eng.cluster_consensus(labels)
     return {k: cc[k] for k in ("cluster_consensus", "item_consensus", "cluster_pairs", "item_pairs")}
+
+
+def vote_refine(eng, labels, max_rounds=16, vote=None):
+    """labels <- top of Engine.vote(labels), repeated until a vote moves no node or `max_rounds`
+    reassignments were made: unlike the components of the agreement graph, the vote can move a node
+    out of the cluster it fell into and empty a fragment cluster.  Returns the dict of the last
+    vote, plus `labels` (int32[n], the partition that vote was made on: a fixpoint, top == labels,
+    when its moved is 0), `rounds` (the reassignments made) and `moved_per_round` (their sizes).
+    `vote`: the voting function, labels -> dict (default eng.vote; the sharded driver passes its own)."""
+    vote = eng.vote if vote is None else vote
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    moved = []
+    while True:
+        res = vote(labels)
+        res["labels"] = labels
+        if res["moved"] == 0 or len(moved) >= max_rounds:
+            break
+        moved.append(res["moved"])
+        labels = np.ascontiguousarray(res["top"], dtype=np.int32)
+    res["rounds"] = len(moved)
+    res["moved_per_round"] = moved
+    return res
+
+
+def vote_result(ref):
+    """What fast_consensus(vote=True) adds to the `consensus` dict, from vote_refine's result."""
+    return {"voted": ref["labels"], "vote_confidence": ref["confidence"], "vote_rounds": ref["rounds"],
+            "vote_moved": ref["moved_per_round"]}
 
 
 def level_of(theta, n_total):
@@ -1084,7 +1178,7 @@ def relabel_for(algorithm):
 
 def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, seed=None, device=0,
                    return_stats=False, rule="fast_consensus", scores=False, truth=None, consensus=None,
-                   coassoc=None, cluster_consensus=False):
+                   coassoc=None, cluster_consensus=False, vote=False):
     """Drop-in for fast_consensus.py:129 ``fast_consensus(G, algorithm, n_p, thresh, delta)``.
 
     G: an undirected networkx Graph (weights are ignored: the reference resets them to 1,
@@ -1130,9 +1224,17 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     ``cluster_consensus`` (float64 per community, in label order: which communities are solid),
     ``item_consensus`` (float64 per node, with its own community: which nodes are firmly placed)
     and the exact integers behind them, ``cluster_pairs`` and ``item_pairs``.
+
+    ``vote=True`` (needs ``consensus``) refines the consensus partition by plurality vote of the
+    n_p partitions (``vote_refine``) and adds to the ``consensus`` dict ``voted`` (int32 per node:
+    the refined partition, ids of the consensus partition), ``vote_confidence`` (float64 per node:
+    the share of the partitions that vote for the node's refined cluster), ``vote_rounds`` and
+    ``vote_moved`` (the nodes reassigned in each round).
     """
     if cluster_consensus and consensus is None:
         raise ValueError("cluster_consensus=True needs consensus (a threshold or \"best\")")
+    if vote and consensus is None:
+        raise ValueError("vote=True needs consensus (a threshold or \"best\")")
     if isinstance(consensus, str) and consensus != "best":
         raise ValueError('consensus must be a threshold in [0, 1] or "best"')
     algo = algo_id(algorithm)
@@ -1163,6 +1265,8 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
             cons = eng.consensus_partition(float(consensus)) if consensus is not None else None
         if cluster_consensus:   # before consensus_scores replaces the labelings
             cons.update(cluster_result(eng, cons["labels"]))
+        if vote:   # before consensus_scores replaces the labelings
+            cons.update(vote_result(vote_refine(eng, cons["labels"])))
         ca = None
         if coassoc is not None:   # before consensus_scores replaces the labelings
             ca = coassoc_result(eng, coassoc_nodes(g.n, coassoc, g.labels, seed), g.labels, cons)

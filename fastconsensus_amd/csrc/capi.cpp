@@ -611,6 +611,53 @@ int fc_cluster_consensus(fc_ctx* ctx, const int32_t* labels, int32_t* ids_out, i
 
 int fc_cluster_consensus_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::cc_ms, ms); }
 
+// plurality vote: the partition's ids on the host, before anything is launched
+static void vote_labels(const Ctx& c, const int32_t* labels) {
+    FC_REQUIRE(labels, FC_EINVAL, "null labels");
+    const uint32_t lim = (uint32_t)c.N;
+    for (int64_t i = 0; i < c.N; ++i)
+        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
+                   "vote label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+}
+
+int fc_vote_map(fc_ctx* ctx, const int32_t* labels, void* dev_mapped, fc_vote_info* info) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    coassoc_state(c);
+    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "the vote handles at most 2048 local replicas");
+    vote_labels(c, labels);
+    FC_REQUIRE(dev_mapped, FC_EINVAL, "null dev_mapped");
+    vote_map(c, labels, (int32_t*)dev_mapped, info);
+    FC_API_END
+}
+
+int fc_vote_count(fc_ctx* ctx, const int32_t* labels, const void* dev_mapped, int n_total, void* dev_top,
+                  void* dev_top_votes, void* dev_own_votes, int64_t* own_hist, fc_vote_info* info) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(n_total >= 1, FC_EINVAL, "n_total must be at least 1");
+    FC_REQUIRE(n_total <= 2048, FC_ELIMIT, "the vote handles at most 2048 replicas");
+    vote_labels(c, labels);
+    FC_REQUIRE(dev_mapped, FC_EINVAL, "null dev_mapped");
+    vote_count(c, labels, (const int32_t*)dev_mapped, n_total, (int32_t*)dev_top, (int32_t*)dev_top_votes,
+               (int32_t*)dev_own_votes, own_hist, info);
+    FC_API_END
+}
+
+int fc_vote(fc_ctx* ctx, const int32_t* labels, void* dev_top, void* dev_top_votes, void* dev_own_votes,
+            int64_t* own_hist, fc_vote_info* info) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    coassoc_state(c);
+    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "the vote handles at most 2048 local replicas");
+    vote_labels(c, labels);
+    vote(c, labels, (int32_t*)dev_top, (int32_t*)dev_top_votes, (int32_t*)dev_own_votes, own_hist, info);
+    FC_API_END
+}
+
+int fc_vote_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::vt_ms, ms); }
+
 int fc_collect_timing(fc_ctx* ctx, fc_stats* st) {
     FC_CTX(ctx)
     FC_API_BEGIN

@@ -125,8 +125,8 @@ struct Graph {
     int32_t max_w = 0;              // largest edge weight (unit-weight graphs skip the weight loads)
 };
 
-// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks)
-constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3;
+// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks; vt_ms by vote.h's VoteMarks)
+constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3, VT_PHASES = 4;
 
 // Every resource goes with the member that holds it (fc_destroy synchronises, then deletes).
 struct Ctx : NoCopy {
@@ -295,6 +295,12 @@ struct Ctx : NoCopy {
     // device time of the last call's phases (timing enabled): segments, count, fallback
     double cc_ms[CC_PHASES] = {};
     DevBuf cc_row, cc_pairs, cc_item, cc_tot, cc_fv1, cc_fv2, cc_fscan;
+    // plurality vote (vote.h): best (count, cluster) per label of one bank of 64 replicas, fc_vote's
+    // mapped [n_r][N], the results by node before they are handed out (top, its votes, own votes),
+    // id flags of P and of top, the nodes left to the sorting kernel, the own-vote histogram, counters
+    // device time of the last call's phases (timing enabled): segments, map, map fallback, count
+    double vt_ms[VT_PHASES] = {};
+    DevBuf vt_best, vt_mapped, vt_top, vt_tv, vt_own, vt_flag, vt_slow, vt_hist, vt_ctr;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = env_int("FC_SCORE_SLOW", 0);
     // longest community one wave streams; longer ones go to the fallback
@@ -433,6 +439,12 @@ void coassoc_hist(Ctx& c, int64_t k, const int32_t* nodes, int64_t* hist);
 // cluster.h: labels on the host in node order, validated by the caller
 void cluster_consensus(Ctx& c, const int32_t* labels, int32_t* ids_out, int64_t* size_out, int64_t* dev_cluster,
                        int64_t* dev_item, fc_cluster_info* info);
+// vote.h: labels on the host in node order, validated by the caller; device outputs may be null
+void vote_map(Ctx& c, const int32_t* labels, int32_t* dev_mapped, fc_vote_info* info);
+void vote_count(Ctx& c, const int32_t* labels, const int32_t* dev_mapped, int n_total, int32_t* dev_top, int32_t* dev_tv,
+                int32_t* dev_own, int64_t* own_hist, fc_vote_info* info);
+void vote(Ctx& c, const int32_t* labels, int32_t* dev_top, int32_t* dev_tv, int32_t* dev_own, int64_t* own_hist,
+          fc_vote_info* info);
 // timing helpers
 int timer_begin(Ctx& c);
 int timer_end(Ctx& c, TimerSlot slot, int begin_ev);   // returns the end event (-1: off)

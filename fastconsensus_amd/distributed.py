@@ -222,13 +222,50 @@ def cluster_consensus_sharded(engine, labels, n_total, device="cuda"):
             "slow_members": int(slow.item()), "n_total": int(n_total)}
 
 
+def vote_sharded(engine, labels, n_total, device="cuda"):
+    """Engine.vote of the partition `labels` over all n_total replicas of a sharded run.  The ranks'
+    `top` cannot be reduced (a plurality is not a sum of pluralities), so each rank maps ITS local
+    labelings onto `labels` (Engine.vote_map), the int32 [n_r, n] results are all-gathered in rank
+    order -- the global replica order of run_sharded's contiguous shards; a count exchange, then the
+    blocks padded to the largest -- and every rank counts the votes over the same [n_total, n] buffer
+    (fc_vote_count).  Returns the dict of Engine.vote, the same on every rank, with
+    mapped_communities and slow_members summed over the ranks.  A rank without replicas
+    contributes no rows; `labels` is the same on every rank."""
+    n = engine.n
+    cuda = "cuda:%d" % engine.device
+    comm = cuda if str(device).startswith("cuda") else "cpu"
+    n_r = engine.replica_info()[0]
+    mine = torch.empty((0, n), dtype=torch.int32, device=cuda)
+    sums = [n_r, 0, 0]
+    if n_r > 0:
+        m = engine.vote_map(labels)
+        mine, sums = m["mapped"], [n_r, m["mapped_communities"], m["slow_members"]]
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        world = dist.get_world_size()
+        cnt = torch.tensor(sums, dtype=torch.int64, device=comm)
+        cnts = [torch.empty_like(cnt) for _ in range(world)]
+        dist.all_gather(cnts, cnt)
+        cnts = torch.stack(cnts).cpu()
+        buf = torch.zeros((max(int(cnts[:, 0].max()), 1), n), dtype=torch.int32, device=comm)
+        buf[:n_r].copy_(mine)
+        bufs = [torch.empty_like(buf) for _ in range(world)]
+        dist.all_gather(bufs, buf)
+        mine = torch.cat([bufs[g][:int(cnts[g, 0])] for g in range(world)]).to(cuda).contiguous()
+        sums = cnts.sum(0).tolist()
+    if mine.shape[0] != int(n_total):
+        raise ValueError("the ranks hold %d labelings, n_total = %d" % (mine.shape[0], n_total))
+    res = engine.vote(labels, dev_mapped=mine, n_total=int(n_total))
+    res["mapped_communities"], res["slow_members"] = int(sums[1]), int(sums[2])
+    return res
+
+
 def _result(res, consensus):
     labels, st = res
     return (labels, st) if consensus is None else (labels, st, st.pop("consensus"))
 
 
 def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, gather=True, out=None,
-                shard_closure=False, out_shared=False, consensus=None):
+                shard_closure=False, out_shared=False, consensus=None, vote=False):
     """Returns (labels [n_p][N] on rank 0 (None elsewhere), stats dict).  `out`: optional
     C-contiguous int32 host array [n_p][N] that rank 0 downloads into (see Engine.run).
     shard_closure: split the closure's attempts over the ranks (world > 1; same result);
@@ -239,7 +276,12 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     consensus) with the dict of Engine.consensus_partition over all n_p final partitions on the
     input graph, the same on every rank.  consensus="best": the threshold is chosen by the
     consensus hierarchy (Engine.consensus_levels over the reduced support); the dict then also
-    holds level, theta, levels, birth and up."""
+    holds level, theta, levels, birth and up.
+    vote: (needs consensus) the consensus partition refined by plurality vote of all n_p final
+    partitions (core.vote_refine over vote_sharded); the dict gains voted, vote_confidence,
+    vote_rounds and vote_moved, the same on every rank."""
+    if vote and consensus is None:
+        raise ValueError("vote=True needs consensus (a threshold or \"best\")")
     if isinstance(consensus, str) and consensus != "best":
         raise ValueError('consensus must be a threshold in [0, 1] or "best"')
     world = dist.get_world_size() if dist.is_initialized() else 1
@@ -253,7 +295,7 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     on_gpu = str(device).startswith("cuda")
     if not on_gpu:
         return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv,
-                             out, shard_closure, out_shared, consensus), consensus)
+                             out, shard_closure, out_shared, consensus, vote), consensus)
     # engine kernels and torch/RCCL ops on ONE explicit stream: no cross-stream races
     # (torch's default stream is the legacy null stream, which the engine cannot adopt)
     stream = torch.cuda.Stream(device=device)
@@ -262,14 +304,14 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     try:
         with torch.cuda.stream(stream):
             return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1,
-                                 louv, out, shard_closure, out_shared, consensus), consensus)
+                                 louv, out, shard_closure, out_shared, consensus, vote), consensus)
     finally:
         stream.synchronize()
         engine.set_stream(None)
 
 
 def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv, out=None,
-          shard_closure=False, out_shared=False, consensus=None):
+          shard_closure=False, out_shared=False, consensus=None, vote=False):
     mine = r1 - r0
     engine.reset_graph()
     n, _, L = engine.graph_info()
@@ -325,6 +367,10 @@ def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank,
     if consensus is not None:
         st["consensus"] = _consensus(engine, consensus if isinstance(consensus, str) else float(consensus), n_p, world,
                                       mine, device)
+        if vote:
+            from .core import vote_refine, vote_result
+            st["consensus"].update(vote_result(vote_refine(
+                engine, st["consensus"]["labels"], vote=lambda lab: vote_sharded(engine, lab, n_p, device))))
     if gather and world > 1 and out_shared and out is not None:
         # every rank downloads its rows into the shared host array; the barrier orders the
         # writes before rank 0 hands the array back

@@ -445,6 +445,55 @@ int fc_cluster_consensus(fc_ctx* ctx, const int32_t* labels, int32_t* ids_out, i
  * fallback (the exact sort-based path). */
 int fc_cluster_consensus_timing(fc_ctx* ctx, double* ms);
 
+/* ---- plurality vote of the labelings on a given partition ------------------------------- */
+/* Relabel-and-vote (Dudoit & Fridlyand; Strehl & Ghosh) for a partition P of the nodes (ids in
+ * [0, n), not necessarily dense) and labelings lab_r.  With C_r[k][d] = the number of nodes v with
+ * P(v) = k and lab_r(v) = d, all integers and all exact:
+ *   map_r(d)     = the cluster k of largest C_r[k][d]; among equals the smallest id
+ *   mapped[r][v] = map_r(lab_r(v))
+ *   votes_v(k)   = the number of r with mapped[r][v] = k;   own[v] = votes_v(P(v))
+ *   top_votes[v] = max_k votes_v(k);  top[v] = the cluster reaching it: P(v) when it is among
+ *                  several that do, otherwise the smallest id
+ * Nothing depends on how a replica numbers its communities.  Only `mapped` depends on which rank
+ * holds a replica: a sharded run all-gathers `mapped` in global replica order and counts on every
+ * rank (the ranks' `top` cannot be reduced).  Read-only like fc_cluster_consensus; the reuse
+ * paragraph at the top of this header holds for these calls too. */
+typedef struct fc_vote_info {
+    int64_t k;                    /* clusters of P */
+    int64_t k_voted;              /* distinct values of top */
+    int64_t moved;                /* nodes with top != P */
+    int64_t unanimous;            /* nodes with own == n_total */
+    int64_t tied;                 /* nodes where more than one cluster reaches top_votes */
+    int64_t mapped_communities;   /* sum over the replicas of their community counts (map calls) */
+    int64_t slow_members;         /* (member, replica) pairs the map's exact fallback handled */
+    int64_t slow_nodes;           /* nodes the vote's sorting fallback handled (more than 8 clusters voted) */
+    int32_t n_total, pad;
+} fc_vote_info;
+/* labels: host int32[n], P in node order.  dev_mapped: device int32[n_r][n], replica-major, node
+ * order, values are ids of P.  Fills k, mapped_communities, slow_members and n_total = n_r.
+ * FC_ESTATE: no graph or no labelings; FC_ELIMIT: more than 2048 local replicas; FC_EINVAL: labels
+ * or dev_mapped NULL, or an id outside [0, n) (the message names the index; checked before any
+ * launch).  Nothing is written on error. */
+int fc_vote_map(fc_ctx* ctx, const int32_t* labels, void* dev_mapped, fc_vote_info* info);
+/* The vote over dev_mapped (device int32[n_total][n] in fc_vote_map's layout, from this rank or
+ * gathered); needs a loaded graph (for n) but no labelings.  dev_top, dev_top_votes, dev_own_votes:
+ * device int32[n] in node order; own_hist: host int64[n_total + 1], own_hist[s] = the nodes with
+ * own == s; any of them may be NULL.  Fills every field of info but the map's three.  FC_ESTATE: no
+ * graph; FC_EINVAL: labels or dev_mapped NULL, an id outside [0, n), n_total < 1, or (found on the
+ * device, before any output is written) a value of dev_mapped that is not an id occurring in
+ * labels; FC_ELIMIT: n_total above 2048. */
+int fc_vote_count(fc_ctx* ctx, const int32_t* labels, const void* dev_mapped, int n_total, void* dev_top,
+                  void* dev_top_votes, void* dev_own_votes, int64_t* own_hist, fc_vote_info* info);
+/* fc_vote_map then fc_vote_count over the local labelings (n_total = n_r), through a buffer the
+ * context owns. */
+int fc_vote(fc_ctx* ctx, const int32_t* labels, void* dev_top, void* dev_top_votes, void* dev_own_votes,
+            int64_t* own_hist, fc_vote_info* info);
+/* Device time (ms, HIP events) of the phases of the last of these three calls made with timing
+ * enabled: ms[4] = segments (upload, sort, run lengths), map (the register-list kernel and the
+ * apply), map fallback (the exact sort-based path), count (the vote and its sorting fallback); a
+ * phase the call did not run is 0. */
+int fc_vote_timing(fc_ctx* ctx, double* ms);
+
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
  * Writes at most m_cap edges into u/v and the planted community of every node. */
