@@ -6,7 +6,7 @@ HIP kernels for gfx950 behind a C-ABI (include/fastconsensus_amd.h).
 """
 from ._lib import FastConsensusError  # noqa: F401
 from .core import (Engine, IdGraph, check_consensus_graph, cluster_consensus, consensus_cdf, cut_tree,  # noqa: F401
-                   device_bytes, fast_consensus, group_to_partition, item_consensus, labels_to_output, level_of, pac,
-                   theta_of, vote_refine)
+                   device_bytes, fast_consensus, group_to_partition, item_consensus, labels_to_output, level_of,
+                   median_moves, median_objective, median_refine, pac, theta_of, vote_refine)
 
 __version__ = "0.1.0"

@@ -36,6 +36,7 @@ SYMBOLS = [
     "fc_coassociation", "fc_coassoc_pairs", "fc_coassoc_hist", "fc_coassoc_timing",
     "fc_cluster_consensus", "fc_cluster_consensus_timing",
     "fc_vote_map", "fc_vote_count", "fc_vote", "fc_vote_timing",
+    "fc_item_affinity", "fc_item_affinity_timing",
 ]
 FC_SCORE_REF = -1
 SCORE_GRAPHS = {"input": 0, "working": 1}
@@ -129,6 +130,17 @@ class VoteInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class AffinityInfo(ctypes.Structure):
+    """fc_affinity_info"""
+    _fields_ = [
+        ("k", ctypes.c_int64), ("queried_clusters", ctypes.c_int64), ("slow_lookups", ctypes.c_int64),
+        ("n_r", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 _lib = None
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
@@ -206,6 +218,9 @@ def load():
     L.fc_vote_count.argtypes = [vp, vp, vp, c_int, vp, vp, vp, vp, vp]
     L.fc_vote.argtypes = [vp, vp, vp, vp, vp, vp, vp]      # the same without dev_mapped and n_total
     L.fc_vote_timing.argtypes = [vp, P(dbl)]
+    # labels (host), npairs, nodes, clusters (host), dev_out, fc_affinity_info
+    L.fc_item_affinity.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    L.fc_item_affinity_timing.argtypes = [vp, P(dbl)]
     _lib = L
     return L
 

@@ -18,6 +18,11 @@ community), no header, floats as ``%.17g`` (``Engine.cluster_consensus``).
 ``--vote`` (with ``--consensus`` or ``--consensus-levels``) votes on the consensus partition
 (``Engine.vote``) and adds ``consensus_t.../vote.tsv``: node, ``community+1``, voted
 ``community+1``, own votes, top votes; one row per node in node order, no header.
+``--median`` (with ``--consensus`` or ``--consensus-levels``) refines the consensus partition (the
+fixpoint of ``vote_refine`` with ``--vote``) by exact one-element moves towards the median partition
+(``median_refine``) and adds ``consensus_t.../median_membership`` (``membership``'s format) and
+``consensus_t.../median.tsv``: one row per round, no header: round, objective, proposed, accepted,
+alone (round 0: the objective before the first round, then zeros).
 """
 import argparse
 import os
@@ -25,7 +30,7 @@ import sys
 
 from ._lib import FC_ALGO_LOUVAIN, FC_ALGO_LOUVAIN_NC
 from .core import (ALGORITHMS, OUT_OF_SCOPE, RULES, Engine, IdGraph, algo_id, best_consensus, coassoc_nodes,
-                   labels_to_output, theta_of)
+                   labels_to_output, median_refine, theta_of, vote_refine)
 
 DEFAULT_TAU = {'louvain': 0.2, 'cnm': 0.7, 'infomap': 0.6, 'lpm': 0.8}   # :426
 
@@ -72,6 +77,8 @@ def build_parser():
     p.add_argument('--cluster-consensus', action='store_true', help=argparse.SUPPRESS)
     # extension: plurality vote of the partitions on the consensus partition
     p.add_argument('--vote', action='store_true', help=argparse.SUPPRESS)
+    # extension: one-element moves of the consensus partition towards the median partition
+    p.add_argument('--median', action='store_true', help=argparse.SUPPRESS)
     return p
 
 
@@ -163,6 +170,22 @@ def write_vote(args, node_labels, labels, vt, root='.'):
             f.write("%s\t%d\t%d\t%d\t%d\n" % (v, c + 1, t + 1, o, tv))
 
 
+def write_median(args, node_labels, md, root='.'):
+    """consensus_t.../median_membership (node+1 <TAB> community+1, sorted by node, like membership)
+    and /median.tsv (round, objective, proposed, accepted, alone; one row per round from round 0,
+    the state before the first, no header).  md: the dict of median_refine."""
+    d = os.path.join(root, 'consensus_' + output_dirs(args)[0][len('out_partitions_'):])
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, 'median_membership'), 'w') as f:
+        for k, v in sorted(zip(node_labels.tolist(), md["labels"].tolist())):
+            f.write(str(k + 1) + "\t" + str(v + 1) + '\n')
+    rows = zip(md["objective"], [0] + md["proposed_per_round"], [0] + md["accepted_per_round"],
+               [0] + md["alone_per_round"])
+    with open(os.path.join(d, 'median.tsv'), 'w') as f:
+        for r, (obj, p, a, al) in enumerate(rows):
+            f.write("%d\t%d\t%d\t%d\t%d\n" % (r, obj, p, a, al))
+
+
 def write_coassoc(node_labels, ids, matrix, root='.'):
     """coassoc.npy (int32 [K, K]) and coassoc_nodes.txt (the K node labels, one per line, in the
     matrix's order), beside the output tree."""
@@ -187,7 +210,9 @@ def main(argv=None):
         raise SystemExit("--cluster-consensus needs --consensus or --consensus-levels")
     if args.vote and args.consensus is None and not args.consensus_levels:
         raise SystemExit("--vote needs --consensus or --consensus-levels")
-    cons = ca = cc = vt = None
+    if args.median and args.consensus is None and not args.consensus_levels:
+        raise SystemExit("--median needs --consensus or --consensus-levels")
+    cons = ca = cc = vt = md = None
     g = IdGraph.from_edgelist_file(args.f)
     if args.coassoc is not None and not 0 <= args.coassoc <= g.n:
         raise SystemExit("--coassoc must lie in [0, %d], the number of nodes" % g.n)
@@ -208,6 +233,8 @@ def main(argv=None):
                 cc = eng.cluster_consensus(cons["labels"])
             if args.vote:
                 vt = eng.vote(cons["labels"])
+            if args.median:
+                md = median_refine(eng, vote_refine(eng, cons["labels"])["labels"] if args.vote else cons["labels"])
             if args.coassoc is not None:
                 ids = coassoc_nodes(g.n, args.coassoc, g.labels, args.seed)
                 ca = (ids, eng.coassociation(ids).cpu().numpy())
@@ -223,6 +250,8 @@ def main(argv=None):
         write_cluster_consensus(args, g.labels, cons["labels"], cc)
     if vt is not None:
         write_vote(args, g.labels, cons["labels"], vt)
+    if md is not None:
+        write_median(args, g.labels, md)
     if ca is not None:
         write_coassoc(g.labels, *ca)
 

@@ -636,6 +636,40 @@ class Engine:
         (set_timing): segments, map, map_fallback, count (0.0 for a phase the call did not run)."""
         return self._phase_timing(self._L.fc_vote_timing, ("segments", "map", "map_fallback", "count"))
 
+    # -- item affinity (fc_item_affinity) ---------------------------------------------------
+    def item_affinity(self, labels, nodes, clusters, dev_out=None):
+        """aff[p] = the co-association of node nodes[p] summed over the members of cluster
+        clusters[p] of the partition `labels` ([n] in node order, ids in [0, n)), over the local
+        labelings, the node itself counted where it is a member: exact integers from the
+        contingency rows, no matrix, cost following the members of the queried clusters plus the
+        queries.  Any order, duplicates allowed, a node may appear against many clusters; an id of
+        [0, n) that does not occur in `labels` gives 0.  Returns a dict: aff int64[npairs] and the
+        fc_affinity_info fields (k, queried_clusters, slow_lookups, n_r).  `dev_out`: a contiguous
+        int64 device tensor of >= npairs elements to write into; ranks add theirs (SUM), see
+        distributed.item_affinity_sharded."""
+        import torch
+        lab = self._vote_labels(labels)
+        nodes, clusters = self._node_ids(nodes), self._node_ids(clusters)
+        if len(nodes) != len(clusters):
+            raise ValueError("nodes and clusters must have the same length")
+        npairs = len(nodes)
+        if dev_out is None:
+            dev_out = torch.empty(max(npairs, 1), dtype=torch.int64, device="cuda:%d" % self.device)
+        elif dev_out.dtype != torch_int64() or dev_out.numel() < npairs or not dev_out.is_contiguous():
+            raise ValueError("dev_out must be a contiguous int64 tensor of >= %d elements" % npairs)
+        info = _lib.AffinityInfo()
+        check(self._L.fc_item_affinity(self._ctx, ptr(lab), npairs, ptr(nodes), ptr(clusters), self._dev(dev_out),
+                                       ctypes.addressof(info)))
+        self._written()
+        out = info.as_dict()
+        out["aff"] = dev_out.reshape(-1)[:npairs].cpu().numpy()
+        return out
+
+    def item_affinity_timing(self):
+        """Device milliseconds of the phases of the last item_affinity made with timing on
+        (set_timing): queries, count, fallback."""
+        return self._phase_timing(self._L.fc_item_affinity_timing, ("queries", "count", "fallback"))
+
     def item_consensus(self, nodes, labels, clusters):
         """int64 [len(nodes), len(clusters)]: entry (i, c) is the co-association of node nodes[i]
         summed over the members of cluster clusters[c] of the partition `labels` ([n] in node
@@ -750,6 +784,151 @@ def vote_result(ref):
     """What fast_consensus(vote=True) adds to the `consensus` dict, from vote_refine's result."""
     return {"voted": ref["labels"], "vote_confidence": ref["confidence"], "vote_rounds": ref["rounds"],
             "vote_moved": ref["moved_per_round"]}
+
+
+def median_objective(pairs_total, size, n_total):
+    """F(P) = 2 * agree(P) - R * sum_k s_k^2 as a Python int: `pairs_total` = agree(P), the sum of
+    cluster_consensus' cluster_pairs over all R = n_total replicas, `size` the cluster sizes.  The
+    summed Mirkin distance of P to the replicas is (T - F) / 2 with T the replicas' summed
+    sum_sq (score_partitions), so the median partition is the P of largest F."""
+    return 2 * int(pairs_total) - int(n_total) * sum(int(s) * int(s) for s in np.asarray(size).reshape(-1))
+
+
+def mean_rand(objective, sum_sq, n, n_total):
+    """The mean Rand index of P with the R = n_total replicas from F(P) and T: 1 - (T - F) / (R n (n - 1))."""
+    if n < 2:
+        return 1.0
+    return 1.0 - (int(sum_sq) - int(objective)) / (int(n_total) * n * (n - 1))
+
+
+def median_moves(labels, nodes, clusters, aff, item_pairs, n_total):
+    """One round of one-element moves towards the median partition, selected so that their gains
+    add exactly.  labels int[n] (ids in [0, n)); (nodes[p], clusters[p]) the candidate targets with
+    aff[p] = aff(node, cluster) over all R = n_total replicas (Engine.item_affinity, ranks summed);
+    item_pairs[v] = aff(v, P(v)) (cluster_consensus).  With s the cluster sizes,
+        pull_own(v) = 2 (item_pairs[v] - R) - R (s_P(v) - 1),   pull(v, b) = 2 aff(v, b) - R s_b,
+        gain(v -> b) = pull(v, b) - pull_own(v),   gain(v alone) = -pull_own(v) when s_P(v) > 1,
+    and a move of v alone changes F (median_objective) by exactly 2 gain.
+    1. Per node (every node, listed or not), the targets are the distinct b != P(v) among its pairs,
+       plus "alone" when its cluster has other members; the best has the largest gain, among equals
+       the smallest cluster id, "alone" losing a tie to a cluster; it is kept when its gain is > 0.
+    2. The kept moves in (gain descending, node ascending) order: winner(c) is the first whose
+       source or target is c.  A move is accepted iff it is winner(source) and goes alone or is
+       also winner(target): the accepted moves touch pairwise disjoint clusters, so F changes by
+       twice the sum of their gains.
+    3. The accepted "alone" movers, by ascending node, take the ids of [0, n) that `labels` does
+       not use, ascending.
+    Every candidate cluster must occur in `labels` (ValueError).  Returns a dict: labels (int32, new),
+    gain (int, the sum over the accepted moves), proposed (the kept moves), accepted, alone."""
+    labels = np.asarray(labels).astype(np.int64).reshape(-1)
+    n = len(labels)
+    nodes = np.asarray(nodes, np.int64).reshape(-1)
+    clusters = np.asarray(clusters, np.int64).reshape(-1)
+    aff = np.asarray(aff, np.int64).reshape(-1)
+    item = np.asarray(item_pairs, np.int64).reshape(-1)
+    R = np.int64(n_total)
+    if not (len(nodes) == len(clusters) == len(aff)) or len(item) != n:
+        raise ValueError("nodes, clusters and aff must have one length, item_pairs the length of labels")
+    size = np.bincount(labels, minlength=n).astype(np.int64)
+    if len(clusters) and (clusters.min() < 0 or clusters.max() >= n or (size[clusters] == 0).any()):
+        raise ValueError("a candidate cluster does not occur in labels")
+    own = labels
+    pull_own = 2 * (item - R) - R * (size[own] - 1)
+    # the candidates: (node, target, gain); "alone" is target n, so that it loses ties to every id
+    other = clusters != own[nodes]
+    cv, cb = nodes[other], clusters[other]
+    cg = 2 * aff[other] - R * size[cb] - pull_own[cv]
+    lone = np.flatnonzero(size[own] > 1)
+    cv = np.concatenate([cv, lone])
+    cb = np.concatenate([cb, np.full(len(lone), n, np.int64)])
+    cg = np.concatenate([cg, -pull_own[lone]])
+    order = np.lexsort((cb, -cg, cv))
+    cv, cb, cg = cv[order], cb[order], cg[order]
+    first = np.ones(len(cv), bool)
+    first[1:] = cv[1:] != cv[:-1]
+    keep = first & (cg > 0)
+    mv, mb, mg = cv[keep], cb[keep], cg[keep]
+    order = np.lexsort((mv, -mg))
+    mv, mb, mg = mv[order], mb[order], mg[order]
+    m = len(mv)
+    pos = np.arange(m, dtype=np.int64)
+    src = own[mv]
+    win = np.full(n + 1, m, np.int64)
+    np.minimum.at(win, src, pos)
+    np.minimum.at(win, mb, pos)   # slot n collects the "alone" movers and is not read
+    alone = mb == n
+    acc = (win[src] == pos) & (alone | (win[np.minimum(mb, n - 1)] == pos))
+    new = labels.copy()
+    go = acc & ~alone
+    new[mv[go]] = mb[go]
+    solo = np.sort(mv[acc & alone])
+    free = np.flatnonzero(size == 0)
+    new[solo] = free[:len(solo)]
+    return {"labels": new.astype(np.int32), "gain": int(mg[acc].sum()), "proposed": int(m),
+            "accepted": int(acc.sum()), "alone": int(len(solo))}
+
+
+def median_refine(eng, labels, max_rounds=64, candidates=None, vote=None, cluster_consensus=None,
+                  item_affinity=None, sum_sq=None):
+    """One-element-move refinement of `labels` towards the median partition of the replicas (the
+    partition of largest mean Rand index with them; Filkov & Skiena, Goder & Filkov).  A round:
+    the vote gives every node's plurality cluster `top` and the replica total R; the candidates are
+    (v, top[v]) for the nodes with top != P (or `candidates`: a pair (nodes, clusters) or a
+    callable labels -> (nodes, clusters)); cluster_consensus gives item_pairs, the sizes and
+    agree(P); item_affinity the candidates' affinities; median_moves selects and applies.  The loop
+    ends when a round accepts nothing (converged) or after `max_rounds` rounds.  A round accepts at
+    most one move per cluster: a refinement, not a from-scratch optimiser.
+    vote, cluster_consensus, item_affinity: the three engine calls, labels -> dict and
+    (labels, nodes, clusters) -> dict (defaults: eng's; the sharded driver passes its own);
+    sum_sq: T, the replicas' summed sum_sq (default: from eng.score_partitions).
+    Returns a dict: labels (int32[n]), rounds, converged, objective (F before the first round and
+    after each, Python ints), proposed_per_round, accepted_per_round, alone_per_round, gain_per_round,
+    mean_rand (before, after) and n_total."""
+    vote = eng.vote if vote is None else vote
+    cluster_consensus = eng.cluster_consensus if cluster_consensus is None else cluster_consensus
+    item_affinity = eng.item_affinity if item_affinity is None else item_affinity
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    n = len(labels)
+    objective, proposed, accepted, alone, gains = [], [], [], [], []
+    converged = False
+    R = None
+    while True:
+        cc = cluster_consensus(labels)
+        if R is None or len(accepted) < max_rounds:
+            v = vote(labels)
+            R = int(v["n_total"])
+        F = median_objective(int(np.asarray(cc["cluster_pairs"], np.int64).sum()), cc["size"], R)
+        objective.append(F)
+        if len(accepted) >= max_rounds:
+            break
+        if candidates is None:
+            top = np.asarray(v["top"])
+            nodes = np.flatnonzero(top != labels)
+            clusters = top[nodes]
+        else:
+            nodes, clusters = candidates(labels) if callable(candidates) else candidates
+        nodes, clusters = np.asarray(nodes, np.int32).reshape(-1), np.asarray(clusters, np.int32).reshape(-1)
+        aff = item_affinity(labels, nodes, clusters)["aff"]
+        mv = median_moves(labels, nodes, clusters, aff, cc["item_pairs"], R)
+        if mv["accepted"] == 0:
+            converged = True
+            break
+        proposed.append(mv["proposed"]); accepted.append(mv["accepted"]); alone.append(mv["alone"])
+        gains.append(mv["gain"])
+        labels = mv["labels"]
+    if sum_sq is None:
+        sum_sq = int(np.asarray(eng.score_partitions()["sum_sq"], np.int64).sum())
+    T = int(sum_sq() if callable(sum_sq) else sum_sq)
+    return {"labels": labels, "rounds": len(accepted), "converged": converged, "objective": objective,
+            "proposed_per_round": proposed, "accepted_per_round": accepted, "alone_per_round": alone,
+            "gain_per_round": gains, "n_total": R,
+            "mean_rand": (mean_rand(objective[0], T, n, R), mean_rand(objective[-1], T, n, R))}
+
+
+def median_result(ref):
+    """What fast_consensus(median=True) adds to the `consensus` dict, from median_refine's result."""
+    return {"median": ref["labels"], "median_objective": ref["objective"], "median_rounds": ref["rounds"],
+            "median_moved": ref["accepted_per_round"], "median_mean_rand": ref["mean_rand"]}
 
 
 def level_of(theta, n_total):
@@ -1178,7 +1357,7 @@ def relabel_for(algorithm):
 
 def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, seed=None, device=0,
                    return_stats=False, rule="fast_consensus", scores=False, truth=None, consensus=None,
-                   coassoc=None, cluster_consensus=False, vote=False):
+                   coassoc=None, cluster_consensus=False, vote=False, median=False):
     """Drop-in for fast_consensus.py:129 ``fast_consensus(G, algorithm, n_p, thresh, delta)``.
 
     G: an undirected networkx Graph (weights are ignored: the reference resets them to 1,
@@ -1230,7 +1409,16 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     the refined partition, ids of the consensus partition), ``vote_confidence`` (float64 per node:
     the share of the partitions that vote for the node's refined cluster), ``vote_rounds`` and
     ``vote_moved`` (the nodes reassigned in each round).
+
+    ``median=True`` (needs ``consensus``) refines the consensus partition -- ``voted`` with
+    ``vote=True`` -- by exact one-element moves towards the median partition of the n_p partitions
+    (``median_refine``) and adds to the ``consensus`` dict ``median`` (int32 per node),
+    ``median_objective`` (F before the first round and after each), ``median_rounds``,
+    ``median_moved`` (the moves accepted in each round) and ``median_mean_rand`` (the mean Rand
+    index with the partitions before and after).
     """
+    if median and consensus is None:
+        raise ValueError("median=True needs consensus (a threshold or \"best\")")
     if cluster_consensus and consensus is None:
         raise ValueError("cluster_consensus=True needs consensus (a threshold or \"best\")")
     if vote and consensus is None:
@@ -1267,6 +1455,8 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
             cons.update(cluster_result(eng, cons["labels"]))
         if vote:   # before consensus_scores replaces the labelings
             cons.update(vote_result(vote_refine(eng, cons["labels"])))
+        if median:   # before consensus_scores replaces the labelings
+            cons.update(median_result(median_refine(eng, cons["voted"] if vote else cons["labels"])))
         ca = None
         if coassoc is not None:   # before consensus_scores replaces the labelings
             ca = coassoc_result(eng, coassoc_nodes(g.n, coassoc, g.labels, seed), g.labels, cons)

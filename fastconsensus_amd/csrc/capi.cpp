@@ -658,6 +658,44 @@ int fc_vote(fc_ctx* ctx, const int32_t* labels, void* dev_top, void* dev_top_vot
 
 int fc_vote_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::vt_ms, ms); }
 
+int fc_item_affinity(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const int32_t* nodes, const int32_t* clusters,
+                     void* dev_out, fc_affinity_info* info) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    coassoc_state(c);
+    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "item affinity handles at most 2048 local replicas");
+    FC_REQUIRE(npairs >= 0, FC_EINVAL, "negative query count");
+    FC_REQUIRE(npairs < ((int64_t)1 << 31), FC_ELIMIT, "item affinity handles fewer than 2^31 queries a call");
+    FC_REQUIRE(labels, FC_EINVAL, "null labels");
+    FC_REQUIRE(npairs == 0 || (nodes && clusters), FC_EINVAL, "null query list");
+    FC_REQUIRE(npairs == 0 || dev_out, FC_EINVAL, "null output buffer");
+    const uint32_t lim = (uint32_t)c.N;
+    for (int64_t i = 0; i < c.N; ++i)
+        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
+                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    for (int64_t p = 0; p < npairs; ++p) {
+        FC_REQUIRE((uint32_t)nodes[p] < lim, FC_EINVAL,
+                   "query node " + std::to_string(nodes[p]) + " at index " + std::to_string(p) + " outside [0, n)");
+        FC_REQUIRE((uint32_t)clusters[p] < lim, FC_EINVAL,
+                   "query cluster " + std::to_string(clusters[p]) + " at index " + std::to_string(p) + " outside [0, n)");
+    }
+    for (double& m : c.ia_ms) m = 0.0;
+    if (npairs == 0) {   // nothing to launch: the cluster count from the host
+        if (info) {
+            std::vector<char> seen((size_t)c.N, 0);
+            int64_t k = 0;
+            for (int64_t i = 0; i < c.N; ++i)
+                if (!seen[labels[i]]) { seen[labels[i]] = 1; ++k; }
+            *info = fc_affinity_info{};
+            info->k = k; info->n_r = c.n_r;
+        }
+    } else
+        item_affinity(c, labels, npairs, nodes, clusters, (int64_t*)dev_out, info);
+    FC_API_END
+}
+
+int fc_item_affinity_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::ia_ms, ms); }
+
 int fc_collect_timing(fc_ctx* ctx, fc_stats* st) {
     FC_CTX(ctx)
     FC_API_BEGIN

@@ -905,3 +905,4 @@ void closure_apply(Ctx& c, int algo, int n_p, const int32_t* counts, int iterati
 #include "coassoc.h"      // co-association (fc_coassociation / fc_coassoc_pairs / fc_coassoc_hist)
 #include "cluster.h"      // cluster and item consensus (fc_cluster_consensus)
 #include "vote.h"         // plurality vote on a partition (fc_vote_map / fc_vote_count / fc_vote)
+#include "affinity.h"     // a node's co-association summed over any cluster (fc_item_affinity)

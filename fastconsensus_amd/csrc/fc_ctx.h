@@ -125,8 +125,8 @@ struct Graph {
     int32_t max_w = 0;              // largest edge weight (unit-weight graphs skip the weight loads)
 };
 
-// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks; vt_ms by vote.h's VoteMarks)
-constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3, VT_PHASES = 4;
+// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks; vt_ms by vote.h's VoteMarks; ia_ms by affinity.h)
+constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3, VT_PHASES = 4, IA_PHASES = 3;
 
 // Every resource goes with the member that holds it (fc_destroy synchronises, then deletes).
 struct Ctx : NoCopy {
@@ -301,6 +301,12 @@ struct Ctx : NoCopy {
     // device time of the last call's phases (timing enabled): segments, map, map fallback, count
     double vt_ms[VT_PHASES] = {};
     DevBuf vt_best, vt_mapped, vt_top, vt_tv, vt_own, vt_flag, vt_slow, vt_hist, vt_ctr;
+    // item affinity (affinity.h): the query lists as uploaded (nodes, then cluster ids), the nodes as
+    // internal vertices, cluster ranks and query indices (by query, then sorted by rank), the queried
+    // clusters with their query counts and offsets, counters, the sums before they are handed out
+    // device time of the last call's phases (timing enabled): queries, count, fallback
+    double ia_ms[IA_PHASES] = {};
+    DevBuf ia_ids, ia_qv, ia_key, ia_idx, ia_qc, ia_qcnt, ia_qoff, ia_ctr, ia_out;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = env_int("FC_SCORE_SLOW", 0);
     // longest community one wave streams; longer ones go to the fallback
@@ -445,6 +451,9 @@ void vote_count(Ctx& c, const int32_t* labels, const int32_t* dev_mapped, int n_
                 int32_t* dev_own, int64_t* own_hist, fc_vote_info* info);
 void vote(Ctx& c, const int32_t* labels, int32_t* dev_top, int32_t* dev_tv, int32_t* dev_own, int64_t* own_hist,
           fc_vote_info* info);
+// affinity.h: labels and the query lists on the host, validated by the caller; npairs >= 1
+void item_affinity(Ctx& c, const int32_t* labels, int64_t npairs, const int32_t* nodes, const int32_t* clusters,
+                   int64_t* dev_out, fc_affinity_info* info);
 // timing helpers
 int timer_begin(Ctx& c);
 int timer_end(Ctx& c, TimerSlot slot, int begin_ev);   // returns the end event (-1: off)

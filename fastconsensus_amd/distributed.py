@@ -259,13 +259,49 @@ def vote_sharded(engine, labels, n_total, device="cuda"):
     return res
 
 
+def item_affinity_sharded(engine, labels, nodes, clusters, device="cuda"):
+    """Engine.item_affinity over every rank's replicas: each rank sums over ITS local labelings, one
+    int64 SUM all-reduce adds the sums, and every rank returns the same dict: aff int64[npairs] and
+    slow_lookups (the ranks' sum).  A rank without replicas contributes zeros; `labels` and the
+    query lists are the same on every rank."""
+    cuda = "cuda:%d" % engine.device
+    npairs = len(np.asarray(nodes).reshape(-1))
+    buf = torch.zeros(npairs + 1, dtype=torch.int64, device=cuda)   # the sums, then slow_lookups
+    if engine.replica_info()[0] > 0:
+        buf[npairs] = engine.item_affinity(labels, nodes, clusters, dev_out=buf)["slow_lookups"]
+    if not str(device).startswith("cuda"):
+        buf = buf.cpu()
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+    out = buf.cpu().numpy()
+    return {"aff": out[:npairs].copy(), "slow_lookups": int(out[npairs])}
+
+
+def median_refine_sharded(engine, labels, n_total, device="cuda", max_rounds=64, candidates=None):
+    """core.median_refine over all n_total replicas of a sharded run: the vote, the cluster consensus
+    and the affinities through vote_sharded, cluster_consensus_sharded and item_affinity_sharded, the
+    replicas' sum_sq added over the ranks.  The selection (core.median_moves) is deterministic on
+    the same integers, so every rank returns the same dict.  `labels` is the same on every rank."""
+    from .core import median_refine
+    t = torch.zeros(1, dtype=torch.int64, device="cuda:%d" % engine.device if str(device).startswith("cuda") else "cpu")
+    if engine.replica_info()[0] > 0:
+        t[0] = int(np.asarray(engine.score_partitions()["sum_sq"], np.int64).sum())
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return median_refine(engine, labels, max_rounds=max_rounds, candidates=candidates,
+                         vote=lambda lab: vote_sharded(engine, lab, n_total, device),
+                         cluster_consensus=lambda lab: cluster_consensus_sharded(engine, lab, n_total, device),
+                         item_affinity=lambda lab, nd, cl: item_affinity_sharded(engine, lab, nd, cl, device),
+                         sum_sq=int(t.item()))
+
+
 def _result(res, consensus):
     labels, st = res
     return (labels, st) if consensus is None else (labels, st, st.pop("consensus"))
 
 
 def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, gather=True, out=None,
-                shard_closure=False, out_shared=False, consensus=None, vote=False):
+                shard_closure=False, out_shared=False, consensus=None, vote=False, median=False):
     """Returns (labels [n_p][N] on rank 0 (None elsewhere), stats dict).  `out`: optional
     C-contiguous int32 host array [n_p][N] that rank 0 downloads into (see Engine.run).
     shard_closure: split the closure's attempts over the ranks (world > 1; same result);
@@ -279,7 +315,13 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     holds level, theta, levels, birth and up.
     vote: (needs consensus) the consensus partition refined by plurality vote of all n_p final
     partitions (core.vote_refine over vote_sharded); the dict gains voted, vote_confidence,
-    vote_rounds and vote_moved, the same on every rank."""
+    vote_rounds and vote_moved, the same on every rank.
+    median: (needs consensus) the consensus partition (`voted` with vote=True) refined by exact
+    one-element moves towards the median partition of all n_p final partitions
+    (median_refine_sharded); the dict gains median, median_objective, median_rounds, median_moved
+    and median_mean_rand, the same on every rank."""
+    if median and consensus is None:
+        raise ValueError("median=True needs consensus (a threshold or \"best\")")
     if vote and consensus is None:
         raise ValueError("vote=True needs consensus (a threshold or \"best\")")
     if isinstance(consensus, str) and consensus != "best":
@@ -295,7 +337,7 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     on_gpu = str(device).startswith("cuda")
     if not on_gpu:
         return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv,
-                             out, shard_closure, out_shared, consensus, vote), consensus)
+                             out, shard_closure, out_shared, consensus, vote, median), consensus)
     # engine kernels and torch/RCCL ops on ONE explicit stream: no cross-stream races
     # (torch's default stream is the legacy null stream, which the engine cannot adopt)
     stream = torch.cuda.Stream(device=device)
@@ -304,14 +346,14 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     try:
         with torch.cuda.stream(stream):
             return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1,
-                                 louv, out, shard_closure, out_shared, consensus, vote), consensus)
+                                 louv, out, shard_closure, out_shared, consensus, vote, median), consensus)
     finally:
         stream.synchronize()
         engine.set_stream(None)
 
 
 def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv, out=None,
-          shard_closure=False, out_shared=False, consensus=None, vote=False):
+          shard_closure=False, out_shared=False, consensus=None, vote=False, median=False):
     mine = r1 - r0
     engine.reset_graph()
     n, _, L = engine.graph_info()
@@ -371,6 +413,10 @@ def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank,
             from .core import vote_refine, vote_result
             st["consensus"].update(vote_result(vote_refine(
                 engine, st["consensus"]["labels"], vote=lambda lab: vote_sharded(engine, lab, n_p, device))))
+        if median:
+            from .core import median_result
+            start = st["consensus"]["voted" if vote else "labels"]
+            st["consensus"].update(median_result(median_refine_sharded(engine, start, n_p, device)))
     if gather and world > 1 and out_shared and out is not None:
         # every rank downloads its rows into the shared host array; the barrier orders the
         # writes before rank 0 hands the array back

@@ -494,6 +494,36 @@ int fc_vote(fc_ctx* ctx, const int32_t* labels, void* dev_top, void* dev_top_vot
  * phase the call did not run is 0. */
 int fc_vote_timing(fc_ctx* ctx, double* ms);
 
+/* ---- co-association of a node with any cluster of a given partition ---------------------- */
+/* For a partition P (ids in [0, n), not necessarily dense) and the local labelings, with
+ * C_r[k][d] = the number of members of cluster k that replica r labels d:
+ *   aff(v, k) = sum_r C_r[k][lab_r(v)] = sum over the members j of k of coassoc(v, j)
+ * v itself counted when P(v) = k, so aff(v, P(v)) is fc_cluster_consensus' item[v].  It is the
+ * numerator of Monti et al.'s item consensus m_i(k) for ANY k, and what a one-element move of the
+ * median-partition objective needs (DESIGN, "Median partition").  Exact integers from the
+ * contingency rows, without the matrix: the cost follows the members of the queried clusters plus
+ * the queries.  A sum over replicas: ranks add theirs (SUM).  Read-only like fc_cluster_consensus;
+ * the reuse paragraph at the top of this header holds for this call too. */
+typedef struct fc_affinity_info {
+    int64_t k;                /* clusters of P */
+    int64_t queried_clusters; /* distinct clusters of P named by the queries */
+    int64_t slow_lookups;     /* (query, replica) pairs the exact fallback answered */
+    int32_t n_r, pad;
+} fc_affinity_info;
+/* out[p] = aff(nodes[p], clusters[p]) over the LOCAL labelings.  labels: host int32[n], P in node
+ * order.  nodes, clusters: host int32[npairs], duplicates and any order allowed, a node may appear
+ * against many clusters; a cluster id in [0, n) that does not occur in labels gives 0.  dev_out:
+ * device int64[npairs].  npairs = 0 launches nothing (the lists and dev_out may then be NULL).
+ * FC_ESTATE: no graph or no labelings; FC_ELIMIT: more than 2048 local replicas, or npairs >= 2^31;
+ * FC_EINVAL: a NULL pointer, or a node, cluster or label id outside [0, n) (the message names the
+ * index; checked before any launch).  Nothing is written on error. */
+int fc_item_affinity(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const int32_t* nodes, const int32_t* clusters,
+                     void* dev_out, fc_affinity_info* info);
+/* Device time (ms, HIP events) of the phases of the last fc_item_affinity made with timing enabled:
+ * ms[3] = queries (upload, segments of P, cluster ranks, sort of the queries), count (the
+ * register-list kernel), fallback (the exact sort-based path). */
+int fc_item_affinity_timing(fc_ctx* ctx, double* ms);
+
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
  * Writes at most m_cap edges into u/v and the planted community of every node. */
