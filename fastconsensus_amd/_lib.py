@@ -37,6 +37,7 @@ SYMBOLS = [
     "fc_cluster_consensus", "fc_cluster_consensus_timing",
     "fc_vote_map", "fc_vote_count", "fc_vote", "fc_vote_timing",
     "fc_item_affinity", "fc_item_affinity_timing",
+    "fc_community_quality", "fc_community_quality_timing",
 ]
 FC_SCORE_REF = -1
 SCORE_GRAPHS = {"input": 0, "working": 1}
@@ -141,6 +142,19 @@ class AffinityInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class QualityInfo(ctypes.Structure):
+    """fc_quality_info"""
+    _fields_ = [
+        ("k", ctypes.c_int64), ("max_size", ctypes.c_int64), ("singletons", ctypes.c_int64),
+        ("parts", ctypes.c_int64), ("disconnected", ctypes.c_int64), ("in_weight", ctypes.c_int64),
+        ("cut_weight", ctypes.c_int64), ("total_degree", ctypes.c_int64),
+    ]
+
+
+# fc_community_record as a numpy record: eight int64 fields
+COMMUNITY_RECORD = np.dtype([(f, np.int64) for f in ("id", "size", "volume", "in_weight", "in_edges", "min_in_degree",
+                                                     "components", "largest_component")])
+
 _lib = None
 _i32p = np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(np.int64, flags="C_CONTIGUOUS")
@@ -221,6 +235,9 @@ def load():
     # labels (host), npairs, nodes, clusters (host), dev_out, fc_affinity_info
     L.fc_item_affinity.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     L.fc_item_affinity_timing.argtypes = [vp, P(dbl)]
+    # graph, labels (host), fc_community_record[n] (host), node_in, node_out, split_out (host or device), fc_quality_info
+    L.fc_community_quality.argtypes = [vp, c_int, vp, vp, vp, vp, vp, vp]
+    L.fc_community_quality_timing.argtypes = [vp, P(dbl)]
     _lib = L
     return L
 

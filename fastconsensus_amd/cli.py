@@ -23,6 +23,13 @@ fixpoint of ``vote_refine`` with ``--vote``) by exact one-element moves towards 
 (``median_refine``) and adds ``consensus_t.../median_membership`` (``membership``'s format) and
 ``consensus_t.../median.tsv``: one row per round, no header: round, objective, proposed, accepted,
 alone (round 0: the objective before the first round, then zeros).
+``--quality`` (with ``--consensus`` or ``--consensus-levels``) asks the graph about the consensus
+communities (``Engine.community_quality``) and adds ``consensus_t.../quality.tsv``: one row per
+community, no header: ``community+1``, size, in_weight, cut, volume, conductance, density,
+components, largest_component (floats as ``%.17g``); and ``consensus_t.../split_membership``
+(``membership``'s format and row order): the partition split into its connected parts,
+``part+1``.  With ``--vote`` / ``--median`` it also writes ``voted_quality.tsv`` (of ``vote.tsv``'s
+voted column) / ``median_quality.tsv`` (of ``median_membership``), the same columns.
 """
 import argparse
 import os
@@ -79,6 +86,8 @@ def build_parser():
     p.add_argument('--vote', action='store_true', help=argparse.SUPPRESS)
     # extension: one-element moves of the consensus partition towards the median partition
     p.add_argument('--median', action='store_true', help=argparse.SUPPRESS)
+    # extension: per-community structure on the graph and the split into connected parts
+    p.add_argument('--quality', action='store_true', help=argparse.SUPPRESS)
     return p
 
 
@@ -186,6 +195,23 @@ def write_median(args, node_labels, md, root='.'):
             f.write("%d\t%d\t%d\t%d\t%d\n" % (r, obj, p, a, al))
 
 
+def write_quality(args, node_labels, q, name='quality.tsv', split=True, root='.'):
+    """consensus_t.../`name` (community+1, size, in_weight, cut, volume, conductance, density,
+    components, largest_component; one row per community in id order, no header, floats as %.17g)
+    and, with `split`, /split_membership (node+1 <TAB> part+1, sorted by node, like membership).
+    q: the dict of Engine.community_quality."""
+    d = os.path.join(root, 'consensus_' + output_dirs(args)[0][len('out_partitions_'):])
+    os.makedirs(d, exist_ok=True)
+    cols = ("size", "in_weight", "cut", "volume", "conductance", "density", "components", "largest_component")
+    with open(os.path.join(d, name), 'w') as f:
+        for row in zip(q["ids"].tolist(), *(q[c].tolist() for c in cols)):
+            f.write("%d\t%d\t%d\t%d\t%d\t%.17g\t%.17g\t%d\t%d\n" % ((row[0] + 1,) + row[1:]))
+    if split:
+        with open(os.path.join(d, 'split_membership'), 'w') as f:
+            for k, v in sorted(zip(node_labels.tolist(), q["split"].tolist())):
+                f.write(str(k + 1) + "\t" + str(v + 1) + '\n')
+
+
 def write_coassoc(node_labels, ids, matrix, root='.'):
     """coassoc.npy (int32 [K, K]) and coassoc_nodes.txt (the K node labels, one per line, in the
     matrix's order), beside the output tree."""
@@ -212,7 +238,9 @@ def main(argv=None):
         raise SystemExit("--vote needs --consensus or --consensus-levels")
     if args.median and args.consensus is None and not args.consensus_levels:
         raise SystemExit("--median needs --consensus or --consensus-levels")
-    cons = ca = cc = vt = md = None
+    if args.quality and args.consensus is None and not args.consensus_levels:
+        raise SystemExit("--quality needs --consensus or --consensus-levels")
+    cons = ca = cc = vt = md = ql = None
     g = IdGraph.from_edgelist_file(args.f)
     if args.coassoc is not None and not 0 <= args.coassoc <= g.n:
         raise SystemExit("--coassoc must lie in [0, %d], the number of nodes" % g.n)
@@ -235,6 +263,12 @@ def main(argv=None):
                 vt = eng.vote(cons["labels"])
             if args.median:
                 md = median_refine(eng, vote_refine(eng, cons["labels"])["labels"] if args.vote else cons["labels"])
+            if args.quality:
+                ql = {"quality.tsv": eng.community_quality(cons["labels"])}
+                if vt is not None:
+                    ql["voted_quality.tsv"] = eng.community_quality(vt["top"])
+                if md is not None:
+                    ql["median_quality.tsv"] = eng.community_quality(md["labels"])
             if args.coassoc is not None:
                 ids = coassoc_nodes(g.n, args.coassoc, g.labels, args.seed)
                 ca = (ids, eng.coassociation(ids).cpu().numpy())
@@ -252,6 +286,8 @@ def main(argv=None):
         write_vote(args, g.labels, cons["labels"], vt)
     if md is not None:
         write_median(args, g.labels, md)
+    for name, q in (ql or {}).items():
+        write_quality(args, g.labels, q, name=name, split=name == 'quality.tsv')
     if ca is not None:
         write_coassoc(g.labels, *ca)
 

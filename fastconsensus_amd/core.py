@@ -698,6 +698,53 @@ class Engine:
             out.index_add_(1, torch.as_tensor(seg[c0:c0 + width], device=dev), mat.to(torch.int64))
         return out.cpu().numpy()
 
+    # -- community quality on the graph (fc_community_quality) ------------------------------
+    def community_quality(self, labels, graph="input", split=True, nodes=True):
+        """What `graph` ("input": G, "working": the consensus graph with its weights) says about
+        every cluster of the partition `labels` ([n] in node order, integer ids in [0, n), not
+        necessarily dense), where cluster_consensus says what the labelings say.  Needs no
+        labelings.  Returns a dict: ids, size, volume (the members' weighted degrees), in_weight
+        and in_edges (the edges inside, each once), min_in_degree, components (connected parts of
+        the induced subgraph), largest_component and cut = volume - 2 in_weight, int64[K] in id
+        order; with `nodes`, node_in / node_out int64[n] (the weight a node sends inside / outside
+        its cluster) and mixing float64[n]; with `split`, split int32[n] (the partition refined to
+        the connected parts, numbered by smallest node); the fc_quality_info fields (k, max_size,
+        singletons, parts, disconnected, in_weight_total, cut_weight, total_degree); and
+        conductance, density and modularity_share float64[K], the module-level functions of those
+        integers."""
+        if graph not in _lib.SCORE_GRAPHS:
+            raise ValueError("graph must be one of %s" % (sorted(_lib.SCORE_GRAPHS),))
+        n = self.n
+        labels = np.asarray(labels)
+        if labels.shape != (n,):
+            raise ValueError("the partition must have shape (%d,)" % n)
+        lab = self._node_ids(labels)
+        rec = np.empty(max(n, 1), _lib.COMMUNITY_RECORD)
+        nin = np.empty(n, np.int64) if nodes else None
+        nout = np.empty(n, np.int64) if nodes else None
+        sp = np.empty(n, np.int32) if split else None
+        info = _lib.QualityInfo()
+        check(self._L.fc_community_quality(self._ctx, _lib.SCORE_GRAPHS[graph], ptr(lab), ptr(rec), ptr(nin),
+                                           ptr(nout), ptr(sp), ctypes.addressof(info)))
+        rec = rec[:info.k]
+        out = {("ids" if f == "id" else f): rec[f].copy() for f in rec.dtype.names}
+        out["cut"] = out["volume"] - 2 * out["in_weight"]
+        for k, _ in info._fields_:
+            out["in_weight_total" if k == "in_weight" else k] = getattr(info, k)
+        if nodes:
+            out.update(node_in=nin, node_out=nout, mixing=mixing(nin, nout))
+        if split:
+            out["split"] = sp
+        out["conductance"] = conductance(out["cut"], out["volume"], info.total_degree)
+        out["density"] = density(out["in_edges"], out["size"])
+        out["modularity_share"] = modularity_share(out["in_weight"], out["volume"], info.total_degree)
+        return out
+
+    def community_quality_timing(self):
+        """Device milliseconds of the phases of the last community_quality made with timing on
+        (set_timing): labels, rows, fold, components."""
+        return self._phase_timing(self._L.fc_community_quality_timing, ("labels", "rows", "fold", "components"))
+
     def nmi_matrix(self):
         """Symmetric [n_r, n_r] float64 NMI between the local replicas (unit diagonal)."""
         return self._pair_matrices()[0]
@@ -756,6 +803,74 @@ def cluster_result(eng, labels):
     """What fast_consensus(cluster_consensus=True) adds to the `consensus` dict."""
     cc = eng.cluster_consensus(labels)
     return {k: cc[k] for k in ("cluster_consensus", "item_consensus", "cluster_pairs", "item_pairs")}
+
+
+def conductance(cut, volume, total_degree):
+    """cut / min(volume, total_degree - volume) per cluster, float64 [K], from the integers of
+    Engine.community_quality; NaN where that minimum is 0 (a cluster without edges, or one that
+    holds every edge end)."""
+    cut, volume = np.asarray(cut, np.int64), np.asarray(volume, np.int64)
+    den = np.minimum(volume, np.int64(total_degree) - volume)
+    out = np.full(cut.shape, np.nan, np.float64)
+    m = den > 0
+    out[m] = cut[m] / den[m]
+    return out
+
+
+def density(in_edges, size):
+    """in_edges / (size (size - 1) / 2) per cluster, float64 [K]; NaN for a cluster of one node."""
+    in_edges, size = np.asarray(in_edges, np.int64), np.asarray(size, np.int64)
+    out = np.full(in_edges.shape, np.nan, np.float64)
+    m = size > 1
+    out[m] = 2 * in_edges[m] / (size[m] * (size[m] - 1))
+    return out
+
+
+def modularity_share(in_weight, volume, total_degree):
+    """2 in_weight / W2 - (volume / W2)^2 per cluster, float64 [K], W2 = total_degree: the terms
+    whose sum is the partition's modularity (zeros on a graph without edges, like the scorer)."""
+    in_weight, volume = np.asarray(in_weight, np.int64), np.asarray(volume, np.int64)
+    if total_degree == 0:
+        return np.zeros(in_weight.shape, np.float64)
+    w2 = float(total_degree)
+    return 2.0 * in_weight / w2 - (volume / w2) ** 2
+
+
+def mixing(node_in, node_out):
+    """node_out / (node_in + node_out) per node, float64 [n]: the share of a node's weight that
+    leaves its cluster (on an LFR graph with its planted partition, the node's empirical mu); NaN
+    for a node without incident weight."""
+    node_in, node_out = np.asarray(node_in, np.int64), np.asarray(node_out, np.int64)
+    tot = node_in + node_out
+    out = np.full(tot.shape, np.nan, np.float64)
+    m = tot != 0
+    out[m] = node_out[m] / tot[m]
+    return out
+
+
+def split_disconnected(eng, labels, graph="input"):
+    """`labels` refined to the connected parts of each of its clusters on `graph`, int32[n], the parts
+    numbered by their smallest node (Engine.community_quality's `split` alone)."""
+    n = eng.n
+    labels = np.asarray(labels)
+    if labels.shape != (n,):
+        raise ValueError("the partition must have shape (%d,)" % n)
+    if graph not in _lib.SCORE_GRAPHS:
+        raise ValueError("graph must be one of %s" % (sorted(_lib.SCORE_GRAPHS),))
+    lab = eng._node_ids(labels)
+    sp = np.empty(n, np.int32)
+    check(eng._L.fc_community_quality(eng._ctx, _lib.SCORE_GRAPHS[graph], ptr(lab), None, None, None, ptr(sp), None))
+    return sp
+
+
+def quality_result(eng, cons):
+    """What fast_consensus(quality=True) adds to the `consensus` dict: `quality` for its labels and
+    `voted_quality` / `median_quality` for the refinements the same call made."""
+    out = {"quality": eng.community_quality(cons["labels"])}
+    for k in ("voted", "median"):
+        if k in cons:
+            out[k + "_quality"] = eng.community_quality(cons[k])
+    return out
 
 
 def vote_refine(eng, labels, max_rounds=16, vote=None):
@@ -1357,7 +1472,7 @@ def relabel_for(algorithm):
 
 def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, seed=None, device=0,
                    return_stats=False, rule="fast_consensus", scores=False, truth=None, consensus=None,
-                   coassoc=None, cluster_consensus=False, vote=False, median=False):
+                   coassoc=None, cluster_consensus=False, vote=False, median=False, quality=False):
     """Drop-in for fast_consensus.py:129 ``fast_consensus(G, algorithm, n_p, thresh, delta)``.
 
     G: an undirected networkx Graph (weights are ignored: the reference resets them to 1,
@@ -1416,7 +1531,15 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     ``median_objective`` (F before the first round and after each), ``median_rounds``,
     ``median_moved`` (the moves accepted in each round) and ``median_mean_rand`` (the mean Rand
     index with the partitions before and after).
+
+    ``quality=True`` (needs ``consensus``) adds ``quality`` to the ``consensus`` dict: what G says
+    about the consensus communities (``Engine.community_quality`` of ``labels``: internal weight,
+    cut, volume, conductance, density, modularity share, connected parts, the split partition and
+    the per-node mixing) and, for each of ``voted`` / ``median`` the same call produced,
+    ``voted_quality`` / ``median_quality``.
     """
+    if quality and consensus is None:
+        raise ValueError("quality=True needs consensus (a threshold or \"best\")")
     if median and consensus is None:
         raise ValueError("median=True needs consensus (a threshold or \"best\")")
     if cluster_consensus and consensus is None:
@@ -1457,6 +1580,8 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
             cons.update(vote_result(vote_refine(eng, cons["labels"])))
         if median:   # before consensus_scores replaces the labelings
             cons.update(median_result(median_refine(eng, cons["voted"] if vote else cons["labels"])))
+        if quality:   # of the graph and the partitions alone: no labelings are read
+            cons.update(quality_result(eng, cons))
         ca = None
         if coassoc is not None:   # before consensus_scores replaces the labelings
             ca = coassoc_result(eng, coassoc_nodes(g.n, coassoc, g.labels, seed), g.labels, cons)

@@ -696,6 +696,23 @@ int fc_item_affinity(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const i
 
 int fc_item_affinity_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::ia_ms, ms); }
 
+int fc_community_quality(fc_ctx* ctx, int graph, const int32_t* labels, fc_community_record* out, int64_t* node_in,
+                         int64_t* node_out, int32_t* split_out, fc_quality_info* info) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    FC_REQUIRE(labels, FC_EINVAL, "null labels");
+    const uint32_t lim = (uint32_t)c.N;
+    for (int64_t i = 0; i < c.N; ++i)
+        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
+                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    community_quality(c, graph, labels, out, node_in, node_out, split_out, info);
+    FC_API_END
+}
+
+int fc_community_quality_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::ql_ms, ms); }
+
 int fc_collect_timing(fc_ctx* ctx, fc_stats* st) {
     FC_CTX(ctx)
     FC_API_BEGIN

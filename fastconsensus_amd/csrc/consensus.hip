@@ -901,6 +901,7 @@ void closure_apply(Ctx& c, int algo, int n_p, const int32_t* counts, int iterati
 #include "analysis.h"     // what the headers below share: support bins, the wave-aggregated add, the phase timer
 #include "score.h"   // partition scoring (fc_score_*): its kernels use the helpers above
 #include "components.h"   // consensus partition (fc_consensus_support / fc_consensus_partition)
+#include "quality.h"      // community quality of a partition on the graph (fc_community_quality)
 #include "levels.h"       // consensus hierarchy (fc_consensus_levels / fc_consensus_cut)
 #include "coassoc.h"      // co-association (fc_coassociation / fc_coassoc_pairs / fc_coassoc_hist)
 #include "cluster.h"      // cluster and item consensus (fc_cluster_consensus)

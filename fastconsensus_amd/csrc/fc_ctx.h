@@ -126,7 +126,7 @@ struct Graph {
 };
 
 // timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks; vt_ms by vote.h's VoteMarks; ia_ms by affinity.h)
-constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3, VT_PHASES = 4, IA_PHASES = 3;
+constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3, VT_PHASES = 4, IA_PHASES = 3, QL_PHASES = 4;
 
 // Every resource goes with the member that holds it (fc_destroy synchronises, then deletes).
 struct Ctx : NoCopy {
@@ -307,6 +307,14 @@ struct Ctx : NoCopy {
     // device time of the last call's phases (timing enabled): queries, count, fallback
     double ia_ms[IA_PHASES] = {};
     DevBuf ia_ids, ia_qv, ia_key, ia_idx, ia_qc, ia_qcnt, ia_qoff, ia_ctr, ia_out;
+    // community quality (quality.h): presence flags of P's ids, their ranks, the ids by rank, dense
+    // cluster ranks by node and by internal vertex, cluster sizes, per-node sums before they are
+    // handed out, the three per-vertex values, the per-cluster accumulators, the split partition,
+    // its part sizes, the records (the union-find runs in cp_parent / cp_flag / cp_rank)
+    // device time of the last call's phases (timing enabled): labels, rows, fold, components
+    double ql_ms[QL_PHASES] = {};
+    DevBuf ql_present, ql_rank, ql_ids, ql_lab, ql_labi, ql_size, ql_nin, ql_nout, ql_vin, ql_vout, ql_vcnt, ql_acc,
+        ql_split, ql_psize, ql_rec;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = env_int("FC_SCORE_SLOW", 0);
     // longest community one wave streams; longer ones go to the fallback
@@ -454,6 +462,9 @@ void vote(Ctx& c, const int32_t* labels, int32_t* dev_top, int32_t* dev_tv, int3
 // affinity.h: labels and the query lists on the host, validated by the caller; npairs >= 1
 void item_affinity(Ctx& c, const int32_t* labels, int64_t npairs, const int32_t* nodes, const int32_t* clusters,
                    int64_t* dev_out, fc_affinity_info* info);
+// quality.h: labels on the host in node order, validated by the caller; any output may be null
+void community_quality(Ctx& c, int graph, const int32_t* labels, fc_community_record* out, int64_t* nin_out,
+                       int64_t* nout_out, int32_t* split_out, fc_quality_info* info);
 // timing helpers
 int timer_begin(Ctx& c);
 int timer_end(Ctx& c, TimerSlot slot, int begin_ev);   // returns the end event (-1: off)

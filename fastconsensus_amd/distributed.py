@@ -301,7 +301,7 @@ def _result(res, consensus):
 
 
 def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, gather=True, out=None,
-                shard_closure=False, out_shared=False, consensus=None, vote=False, median=False):
+                shard_closure=False, out_shared=False, consensus=None, vote=False, median=False, quality=False):
     """Returns (labels [n_p][N] on rank 0 (None elsewhere), stats dict).  `out`: optional
     C-contiguous int32 host array [n_p][N] that rank 0 downloads into (see Engine.run).
     shard_closure: split the closure's attempts over the ranks (world > 1; same result);
@@ -319,7 +319,13 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     median: (needs consensus) the consensus partition (`voted` with vote=True) refined by exact
     one-element moves towards the median partition of all n_p final partitions
     (median_refine_sharded); the dict gains median, median_objective, median_rounds, median_moved
-    and median_mean_rand, the same on every rank."""
+    and median_mean_rand, the same on every rank.
+    quality: (needs consensus) what the input graph says about the consensus communities
+    (Engine.community_quality): the dict gains quality and, for each of voted / median the call
+    produced, voted_quality / median_quality.  A property of the graph and the partition alone, so
+    every rank computes it locally and no collective is needed."""
+    if quality and consensus is None:
+        raise ValueError("quality=True needs consensus (a threshold or \"best\")")
     if median and consensus is None:
         raise ValueError("median=True needs consensus (a threshold or \"best\")")
     if vote and consensus is None:
@@ -337,7 +343,7 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     on_gpu = str(device).startswith("cuda")
     if not on_gpu:
         return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv,
-                             out, shard_closure, out_shared, consensus, vote, median), consensus)
+                             out, shard_closure, out_shared, consensus, vote, median, quality), consensus)
     # engine kernels and torch/RCCL ops on ONE explicit stream: no cross-stream races
     # (torch's default stream is the legacy null stream, which the engine cannot adopt)
     stream = torch.cuda.Stream(device=device)
@@ -346,14 +352,14 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     try:
         with torch.cuda.stream(stream):
             return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1,
-                                 louv, out, shard_closure, out_shared, consensus, vote, median), consensus)
+                                 louv, out, shard_closure, out_shared, consensus, vote, median, quality), consensus)
     finally:
         stream.synchronize()
         engine.set_stream(None)
 
 
 def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv, out=None,
-          shard_closure=False, out_shared=False, consensus=None, vote=False, median=False):
+          shard_closure=False, out_shared=False, consensus=None, vote=False, median=False, quality=False):
     mine = r1 - r0
     engine.reset_graph()
     n, _, L = engine.graph_info()
@@ -417,6 +423,9 @@ def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank,
             from .core import median_result
             start = st["consensus"]["voted" if vote else "labels"]
             st["consensus"].update(median_result(median_refine_sharded(engine, start, n_p, device)))
+        if quality:
+            from .core import quality_result
+            st["consensus"].update(quality_result(engine, st["consensus"]))
     if gather and world > 1 and out_shared and out is not None:
         # every rank downloads its rows into the shared host array; the barrier orders the
         # writes before rank 0 hands the array back

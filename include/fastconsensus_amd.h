@@ -27,6 +27,8 @@
  *     next fc_load_graph; fc_consensus_cut reads the hierarchy of the last
  *     fc_consensus_levels, kept until the next fc_load_graph; fc_load_graph drops the
  *     reference labeling of fc_score_set_reference and the labelings.
+ *     fc_community_quality depends on the chosen graph and its arguments alone and leaves graph,
+ *     labelings, reference, hierarchy and random state as they were.
  */
 #ifndef FASTCONSENSUS_AMD_H
 #define FASTCONSENSUS_AMD_H
@@ -523,6 +525,48 @@ int fc_item_affinity(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const i
  * ms[3] = queries (upload, segments of P, cluster ranks, sort of the queries), count (the
  * register-list kernel), fallback (the exact sort-based path). */
 int fc_item_affinity_timing(fc_ctx* ctx, double* ms);
+
+/* ---- community quality of a given partition on the graph ---------------------------------- */
+/* H = the chosen graph (FC_SCORE_GRAPH_*), P a partition (ids in [0, n), not necessarily dense: a
+ * consensus cut, `voted`, `median`, a replica, a ground truth).  What the GRAPH says about each
+ * cluster of P, where fc_cluster_consensus says what the labelings say: internal weight, volume and
+ * from them the cut (volume - 2 * in_weight, not stored), conductance, density and the cluster's
+ * share of modularity; the number of connected parts of the subgraph its members induce (level-0
+ * Louvain and LPA, and the one-node moves of the vote and median refinements, can leave a cluster
+ * in several pieces); per node the weight it sends inside and outside its cluster.  Exact
+ * integers.  The call reads no labelings: it works on a context that has only loaded a graph, and
+ * it is the same on every rank (no collective).  Read-only: the reuse paragraph at the top of
+ * this header holds for this call too. */
+typedef struct fc_community_record {   /* one record per cluster of P, ids ascending */
+    int64_t id, size;
+    int64_t volume;          /* sum of the members' weighted degrees in H */
+    int64_t in_weight;       /* sum of w over the edges of H with both ends in the cluster, each once */
+    int64_t in_edges;        /* the number of those edges (weight-0 edges of the working graph count) */
+    int64_t min_in_degree;   /* min over the members of the number of neighbours inside the cluster */
+    int64_t components;      /* connected parts of the subgraph of H induced by the members */
+    int64_t largest_component;
+} fc_community_record;
+typedef struct fc_quality_info {
+    int64_t k, max_size, singletons;
+    int64_t parts;           /* sum of components = clusters of the split partition */
+    int64_t disconnected;    /* clusters with components > 1 */
+    int64_t in_weight, cut_weight;   /* totals; every cut edge counted once */
+    int64_t total_degree;    /* W2 of H */
+} fc_quality_info;
+/* labels: host int32[n], P in node order.  out: host, capacity n records, the first info->k are
+ * written.  node_in[v] / node_out[v]: the weight of v's incident edges whose other end is / is not
+ * in P(v), int64[n]; split_out: P refined to the connected parts of each cluster, int32[n], the
+ * parts numbered 0..parts-1 by their smallest node id (fc_get_labels' renumber convention).  These
+ * three may be host memory or device buffers of the context's GPU.  Any output may be NULL, and a
+ * phase whose outputs are all NULL does not run.  FC_ESTATE: no graph; FC_EINVAL: labels NULL, an
+ * unknown graph, or an id outside [0, n) (the message names the index; checked before any
+ * launch).  Nothing is written on error. */
+int fc_community_quality(fc_ctx* ctx, int graph, const int32_t* labels, fc_community_record* out, int64_t* node_in,
+                         int64_t* node_out, int32_t* split_out, fc_quality_info* info);
+/* Device time (ms, HIP events) of the phases of the last fc_community_quality made with timing
+ * enabled: ms[4] = labels (upload, id ranks, sizes), rows (the CSR pass), fold (per-vertex values to
+ * per-cluster sums), components (union-find, split partition, parts, records and totals). */
+int fc_community_quality_timing(fc_ctx* ctx, double* ms);
 
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
