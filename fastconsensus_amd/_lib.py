@@ -38,6 +38,7 @@ SYMBOLS = [
     "fc_vote_map", "fc_vote_count", "fc_vote", "fc_vote_timing",
     "fc_item_affinity", "fc_item_affinity_timing",
     "fc_community_quality", "fc_community_quality_timing",
+    "fc_community_graph", "fc_community_graph_timing", "fc_cluster_coassoc", "fc_cluster_coassoc_timing",
 ]
 FC_SCORE_REF = -1
 SCORE_GRAPHS = {"input": 0, "working": 1}
@@ -142,6 +143,17 @@ class AffinityInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class ClusterPairInfo(ctypes.Structure):
+    """fc_cluster_pair_info"""
+    _fields_ = [
+        ("k", ctypes.c_int64), ("listed_clusters", ctypes.c_int64), ("walked_members", ctypes.c_int64),
+        ("slow_lookups", ctypes.c_int64), ("n_r", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class QualityInfo(ctypes.Structure):
     """fc_quality_info"""
     _fields_ = [
@@ -238,6 +250,12 @@ def load():
     # graph, labels (host), fc_community_record[n] (host), node_in, node_out, split_out (host or device), fc_quality_info
     L.fc_community_quality.argtypes = [vp, c_int, vp, vp, vp, vp, vp, vp]
     L.fc_community_quality_timing.argtypes = [vp, P(dbl)]
+    # graph, labels (host), capacity, a, b, weight, edges (host or device, or NULL), npairs
+    L.fc_community_graph.argtypes = [vp, c_int, vp, i64, vp, vp, vp, vp, P(i64)]
+    L.fc_community_graph_timing.argtypes = [vp, P(dbl)]
+    # labels (host), npairs, a, b (host), dev_out, fc_cluster_pair_info
+    L.fc_cluster_coassoc.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    L.fc_cluster_coassoc_timing.argtypes = [vp, P(dbl)]
     _lib = L
     return L
 

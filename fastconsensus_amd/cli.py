@@ -30,6 +30,13 @@ components, largest_component (floats as ``%.17g``); and ``consensus_t.../split_
 (``membership``'s format and row order): the partition split into its connected parts,
 ``part+1``.  With ``--vote`` / ``--median`` it also writes ``voted_quality.tsv`` (of ``vote.tsv``'s
 voted column) / ``median_quality.tsv`` (of ``median_membership``), the same columns.
+``--merge`` (with ``--consensus`` or ``--consensus-levels``) runs last, on ``median_membership``'s
+partition with ``--median``, else on the fixpoint of ``vote_refine`` with ``--vote``, else on the
+consensus partition: cluster merges towards the median partition (``merge_refine``).  It adds
+``consensus_t.../merge_membership`` (``membership``'s format) and ``consensus_t.../merge.tsv``: one
+row per round, no header: round, objective, k, pairs, proposed, accepted (round 0: the objective
+and the clusters before the first round, then zeros).  With ``--quality`` it also writes
+``merged_quality.tsv`` (of ``merge_membership``), ``quality.tsv``'s columns.
 """
 import argparse
 import os
@@ -37,7 +44,7 @@ import sys
 
 from ._lib import FC_ALGO_LOUVAIN, FC_ALGO_LOUVAIN_NC
 from .core import (ALGORITHMS, OUT_OF_SCOPE, RULES, Engine, IdGraph, algo_id, best_consensus, coassoc_nodes,
-                   labels_to_output, median_refine, theta_of, vote_refine)
+                   labels_to_output, median_refine, merge_refine, theta_of, vote_refine)
 
 DEFAULT_TAU = {'louvain': 0.2, 'cnm': 0.7, 'infomap': 0.6, 'lpm': 0.8}   # :426
 
@@ -88,6 +95,8 @@ def build_parser():
     p.add_argument('--median', action='store_true', help=argparse.SUPPRESS)
     # extension: per-community structure on the graph and the split into connected parts
     p.add_argument('--quality', action='store_true', help=argparse.SUPPRESS)
+    # extension: cluster merges of the consensus partition towards the median partition
+    p.add_argument('--merge', action='store_true', help=argparse.SUPPRESS)
     return p
 
 
@@ -195,6 +204,22 @@ def write_median(args, node_labels, md, root='.'):
             f.write("%d\t%d\t%d\t%d\t%d\n" % (r, obj, p, a, al))
 
 
+def write_merge(args, node_labels, mg, root='.'):
+    """consensus_t.../merge_membership (node+1 <TAB> community+1, sorted by node, like membership)
+    and /merge.tsv (round, objective, k, pairs, proposed, accepted; one row per round from round 0,
+    the state before the first, no header).  mg: the dict of merge_refine."""
+    d = os.path.join(root, 'consensus_' + output_dirs(args)[0][len('out_partitions_'):])
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, 'merge_membership'), 'w') as f:
+        for k, v in sorted(zip(node_labels.tolist(), mg["labels"].tolist())):
+            f.write(str(k + 1) + "\t" + str(v + 1) + '\n')
+    rows = zip(mg["objective"], mg["k_per_round"], [0] + mg["pairs_per_round"], [0] + mg["proposed_per_round"],
+               [0] + mg["accepted_per_round"])
+    with open(os.path.join(d, 'merge.tsv'), 'w') as f:
+        for r, row in enumerate(rows):
+            f.write("%d\t%d\t%d\t%d\t%d\t%d\n" % ((r,) + row))
+
+
 def write_quality(args, node_labels, q, name='quality.tsv', split=True, root='.'):
     """consensus_t.../`name` (community+1, size, in_weight, cut, volume, conductance, density,
     components, largest_component; one row per community in id order, no header, floats as %.17g)
@@ -240,7 +265,9 @@ def main(argv=None):
         raise SystemExit("--median needs --consensus or --consensus-levels")
     if args.quality and args.consensus is None and not args.consensus_levels:
         raise SystemExit("--quality needs --consensus or --consensus-levels")
-    cons = ca = cc = vt = md = ql = None
+    if args.merge and args.consensus is None and not args.consensus_levels:
+        raise SystemExit("--merge needs --consensus or --consensus-levels")
+    cons = ca = cc = vt = md = ql = mg = None
     g = IdGraph.from_edgelist_file(args.f)
     if args.coassoc is not None and not 0 <= args.coassoc <= g.n:
         raise SystemExit("--coassoc must lie in [0, %d], the number of nodes" % g.n)
@@ -269,6 +296,12 @@ def main(argv=None):
                     ql["voted_quality.tsv"] = eng.community_quality(vt["top"])
                 if md is not None:
                     ql["median_quality.tsv"] = eng.community_quality(md["labels"])
+            if args.merge:
+                start = md["labels"] if md is not None else \
+                    vote_refine(eng, cons["labels"])["labels"] if args.vote else cons["labels"]
+                mg = merge_refine(eng, start)
+                if args.quality:
+                    ql["merged_quality.tsv"] = eng.community_quality(mg["labels"])
             if args.coassoc is not None:
                 ids = coassoc_nodes(g.n, args.coassoc, g.labels, args.seed)
                 ca = (ids, eng.coassociation(ids).cpu().numpy())
@@ -286,6 +319,8 @@ def main(argv=None):
         write_vote(args, g.labels, cons["labels"], vt)
     if md is not None:
         write_median(args, g.labels, md)
+    if mg is not None:
+        write_merge(args, g.labels, mg)
     for name, q in (ql or {}).items():
         write_quality(args, g.labels, q, name=name, split=name == 'quality.tsv')
     if ca is not None:

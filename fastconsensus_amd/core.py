@@ -745,6 +745,61 @@ class Engine:
         (set_timing): labels, rows, fold, components."""
         return self._phase_timing(self._L.fc_community_quality_timing, ("labels", "rows", "fold", "components"))
 
+    # -- cluster merges (fc_community_graph / fc_cluster_coassoc) ---------------------------
+    def community_graph(self, labels, graph="input"):
+        """The community graph (quotient graph) of the partition `labels` ([n] in node order,
+        integer ids in [0, n), not necessarily dense) on `graph` ("input": G, "working": the
+        consensus graph with its weights): which clusters touch, and how strongly.  Needs no
+        labelings.  Returns a dict: a, b int32[npairs] (the distinct cluster pairs a < b joined by
+        at least one edge, ascending by (a, b)), weight int64[npairs] (the sum of w over the joining
+        edges), edges int64[npairs] (their number) and npairs."""
+        cap = max(self._graph_edges(graph), 1)   # every edge its own pair at the most; the pages stay untouched
+        lab = self._vote_labels(labels)
+        a, b = np.empty(cap, np.int32), np.empty(cap, np.int32)
+        w, e = np.empty(cap, np.int64), np.empty(cap, np.int64)
+        cnt = ctypes.c_int64(0)
+        check(self._L.fc_community_graph(self._ctx, _lib.SCORE_GRAPHS[graph], ptr(lab), cap, ptr(a), ptr(b), ptr(w),
+                                         ptr(e), ctypes.byref(cnt)))
+        k = cnt.value
+        return {"a": a[:k].copy(), "b": b[:k].copy(), "weight": w[:k].copy(), "edges": e[:k].copy(), "npairs": int(k)}
+
+    def community_graph_timing(self):
+        """Device milliseconds of the phases of the last community_graph made with timing on
+        (set_timing): labels, emit, sort, pairs."""
+        return self._phase_timing(self._L.fc_community_graph_timing, ("labels", "emit", "sort", "pairs"))
+
+    def cluster_coassoc(self, labels, a, b, dev_out=None):
+        """x[p] = X(a[p], b[p]): the co-association summed over the member pairs (i in a[p], j in
+        b[p]) of two clusters of the partition `labels` ([n] in node order, ids in [0, n)), over the
+        local labelings: exact integers from the contingency rows, no matrix.  Duplicates, both
+        orders and a[p] == b[p] are allowed (X(a, a) is cluster_consensus' cluster_pairs); an id of
+        [0, n) that does not occur in `labels` gives 0.  Returns a dict: x int64[npairs] and the
+        fc_cluster_pair_info fields (k, listed_clusters, walked_members, slow_lookups, n_r).
+        `dev_out`: a contiguous int64 device tensor of >= npairs elements to write into; ranks add
+        theirs (SUM), see distributed.cluster_coassoc_sharded."""
+        import torch
+        lab = self._vote_labels(labels)
+        a, b = self._node_ids(a), self._node_ids(b)
+        if len(a) != len(b):
+            raise ValueError("a and b must have the same length")
+        npairs = len(a)
+        if dev_out is None:
+            dev_out = torch.empty(max(npairs, 1), dtype=torch.int64, device="cuda:%d" % self.device)
+        elif dev_out.dtype != torch_int64() or dev_out.numel() < npairs or not dev_out.is_contiguous():
+            raise ValueError("dev_out must be a contiguous int64 tensor of >= %d elements" % npairs)
+        info = _lib.ClusterPairInfo()
+        check(self._L.fc_cluster_coassoc(self._ctx, ptr(lab), npairs, ptr(a), ptr(b), self._dev(dev_out),
+                                         ctypes.addressof(info)))
+        self._written()
+        out = info.as_dict()
+        out["x"] = dev_out.reshape(-1)[:npairs].cpu().numpy()
+        return out
+
+    def cluster_coassoc_timing(self):
+        """Device milliseconds of the phases of the last cluster_coassoc made with timing on
+        (set_timing): pairs, count, fallback."""
+        return self._phase_timing(self._L.fc_cluster_coassoc_timing, ("pairs", "count", "fallback"))
+
     def nmi_matrix(self):
         """Symmetric [n_r, n_r] float64 NMI between the local replicas (unit diagonal)."""
         return self._pair_matrices()[0]
@@ -1044,6 +1099,138 @@ def median_result(ref):
     """What fast_consensus(median=True) adds to the `consensus` dict, from median_refine's result."""
     return {"median": ref["labels"], "median_objective": ref["objective"], "median_rounds": ref["rounds"],
             "median_moved": ref["accepted_per_round"], "median_mean_rand": ref["mean_rand"]}
+
+
+def between_consensus(x, size_a, size_b, n_total):
+    """x / (n_total s_a s_b) as float64: the mean consensus between two clusters from
+    Engine.cluster_coassoc's integers summed over all n_total replicas, the between-cluster
+    counterpart of cluster_consensus (NaN where a size is 0)."""
+    x = np.asarray(x, np.float64)
+    den = float(n_total) * np.asarray(size_a, np.float64) * np.asarray(size_b, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den > 0, x / den, np.nan)
+
+
+def merge_moves(labels, a, b, x, n_total):
+    """One round of cluster merges towards the median partition, selected so that their gains add
+    exactly.  labels int[n] (ids in [0, n)); (a[p], b[p]) the candidate cluster pairs with x[p] =
+    X(a, b) over all R = n_total replicas (Engine.cluster_coassoc, ranks summed).  With s the
+    cluster sizes, gain(a, b) = 2 X(a, b) - R s_a s_b, and joining a and b alone changes F
+    (median_objective) by exactly 2 gain.
+    1. Every candidate is oriented so that a < b; a == b and repeated pairs are dropped.
+    2. The pairs with gain > 0 are kept.
+    3. They are ordered by (gain descending, a ascending, b ascending).
+    4. In that order a pair is accepted iff neither of its clusters belongs to a pair accepted
+       earlier: the accepted merges touch pairwise disjoint clusters, so F changes by twice the sum
+       of their gains.
+    5. The members of b take the id a.
+    Deterministic on identical integers, so every rank of a sharded run selects the same merges.
+    Returns a dict: labels (int32, new), gain (int, the sum over the accepted merges), proposed (the
+    kept pairs), accepted."""
+    labels = np.asarray(labels).astype(np.int64).reshape(-1)
+    n = len(labels)
+    a = np.asarray(a, np.int64).reshape(-1)
+    b = np.asarray(b, np.int64).reshape(-1)
+    x = np.asarray(x, np.int64).reshape(-1)
+    if not (len(a) == len(b) == len(x)):
+        raise ValueError("a, b and x must have one length")
+    if len(a) and (min(a.min(), b.min()) < 0 or max(a.max(), b.max()) >= n):
+        raise ValueError("a candidate cluster id lies outside [0, n)")
+    lo, hi = np.minimum(a, b), np.maximum(a, b)
+    keep = lo != hi
+    lo, hi, x = lo[keep], hi[keep], x[keep]
+    _, first = np.unique(lo * n + hi, return_index=True)
+    lo, hi, x = lo[first], hi[first], x[first]
+    size = np.bincount(labels, minlength=n).astype(np.int64)
+    gain = 2 * x - np.int64(n_total) * size[lo] * size[hi]
+    pos = gain > 0
+    lo, hi, gain = lo[pos], hi[pos], gain[pos]
+    order = np.lexsort((hi, lo, -gain))
+    lo, hi, gain = lo[order], hi[order], gain[order]
+    used = np.zeros(n, bool)
+    target = np.arange(n, dtype=np.int64)
+    total, accepted = 0, 0
+    for ca, cb, cg in zip(lo.tolist(), hi.tolist(), gain.tolist()):
+        if used[ca] or used[cb]:
+            continue
+        used[ca] = used[cb] = True
+        target[cb] = ca
+        total += cg
+        accepted += 1
+    return {"labels": target[labels].astype(np.int32), "gain": int(total), "proposed": int(len(lo)),
+            "accepted": int(accepted)}
+
+
+def merge_refine(eng, labels, graph="input", max_rounds=64, candidates=None, community_graph=None,
+                 cluster_coassoc=None, cluster_consensus=None, sum_sq=None):
+    """Agglomerative refinement of `labels` towards the median partition of the replicas (Filkov &
+    Skiena, Goder & Filkov): the move median_refine lacks.  A round: the candidates are the pairs of
+    the community graph of the current partition on `graph` (or `candidates`: a pair (a, b) of
+    cluster-id lists or a callable labels -> (a, b)); cluster_coassoc gives their X; merge_moves
+    selects and applies.  The loop ends when a round accepts nothing (converged) or after
+    `max_rounds` rounds.  objective[0] comes from one cluster_consensus call; every later entry is
+    the one before plus twice the round's gain (exact: DESIGN, "Cluster merges").  A round accepts at
+    most one merge per cluster, only adjacent clusters are candidates, and nothing is ever split.
+    community_graph, cluster_coassoc, cluster_consensus: the three engine calls, labels -> dict,
+    (labels, a, b) -> dict and labels -> dict (defaults: eng's; the sharded driver passes its own);
+    sum_sq: T, the replicas' summed sum_sq (default: from eng.score_partitions).
+    Returns a dict: labels (int32[n]), rounds, converged, objective (F before the first round and
+    after each), pairs_per_round, proposed_per_round, accepted_per_round, gain_per_round,
+    k_per_round (the clusters before the first round and after each) and mean_rand (before, after);
+    the lists hold Python ints."""
+    if community_graph is None:
+        def community_graph(lab):
+            return eng.community_graph(lab, graph)
+    cluster_coassoc = eng.cluster_coassoc if cluster_coassoc is None else cluster_coassoc
+    cluster_consensus = eng.cluster_consensus if cluster_consensus is None else cluster_consensus
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    n = len(labels)
+    cc = cluster_consensus(labels)
+    R = int(cc["n_total"] if "n_total" in cc else cc["n_r"])
+    objective = [median_objective(int(np.asarray(cc["cluster_pairs"], np.int64).sum()), cc["size"], R)]
+    ks = [int(len(cc["size"]))]
+    pairs, proposed, accepted, gains = [], [], [], []
+    converged = False
+    while len(accepted) < max_rounds:
+        if candidates is None:
+            cg = community_graph(labels)
+            a, b = cg["a"], cg["b"]
+        else:
+            a, b = candidates(labels) if callable(candidates) else candidates
+        a, b = np.asarray(a, np.int32).reshape(-1), np.asarray(b, np.int32).reshape(-1)
+        x = cluster_coassoc(labels, a, b)["x"] if len(a) else np.zeros(0, np.int64)
+        mv = merge_moves(labels, a, b, x, R)
+        if mv["accepted"] == 0:
+            converged = True
+            break
+        pairs.append(int(len(a))); proposed.append(mv["proposed"]); accepted.append(mv["accepted"])
+        gains.append(mv["gain"])
+        objective.append(objective[-1] + 2 * mv["gain"])
+        ks.append(ks[-1] - mv["accepted"])
+        labels = mv["labels"]
+    if sum_sq is None:
+        sum_sq = int(np.asarray(eng.score_partitions()["sum_sq"], np.int64).sum())
+    T = int(sum_sq() if callable(sum_sq) else sum_sq)
+    return {"labels": labels, "rounds": len(accepted), "converged": converged, "objective": objective,
+            "pairs_per_round": pairs, "proposed_per_round": proposed, "accepted_per_round": accepted,
+            "gain_per_round": gains, "k_per_round": ks,
+            "mean_rand": (mean_rand(objective[0], T, n, R), mean_rand(objective[-1], T, n, R))}
+
+
+def merge_result(ref):
+    """What fast_consensus(merge=True) adds to the `consensus` dict, from merge_refine's result."""
+    return {"merged": ref["labels"], "merged_objective": ref["objective"], "merged_rounds": ref["rounds"],
+            "merged_accepted": ref["accepted_per_round"], "merged_k": ref["k_per_round"],
+            "merged_mean_rand": ref["mean_rand"]}
+
+
+def merge_start(cons):
+    """The partition merge=True starts from: `median` if it was produced, else `voted`, else the
+    consensus partition."""
+    for k in ("median", "voted"):
+        if k in cons:
+            return cons[k]
+    return cons["labels"]
 
 
 def level_of(theta, n_total):
@@ -1472,7 +1659,7 @@ def relabel_for(algorithm):
 
 def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, seed=None, device=0,
                    return_stats=False, rule="fast_consensus", scores=False, truth=None, consensus=None,
-                   coassoc=None, cluster_consensus=False, vote=False, median=False, quality=False):
+                   coassoc=None, cluster_consensus=False, vote=False, median=False, quality=False, merge=False):
     """Drop-in for fast_consensus.py:129 ``fast_consensus(G, algorithm, n_p, thresh, delta)``.
 
     G: an undirected networkx Graph (weights are ignored: the reference resets them to 1,
@@ -1537,7 +1724,17 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     cut, volume, conductance, density, modularity share, connected parts, the split partition and
     the per-node mixing) and, for each of ``voted`` / ``median`` the same call produced,
     ``voted_quality`` / ``median_quality``.
+
+    ``merge=True`` (needs ``consensus``) runs last, on ``median`` if it was produced, else on
+    ``voted``, else on the consensus partition: cluster merges towards the median partition of the
+    n_p partitions (``merge_refine``: the community graph's pairs, their exact co-association, a
+    greedy matching of the positive gains).  It adds to the ``consensus`` dict ``merged`` (int32
+    per node), ``merged_objective`` (F before the first round and after each), ``merged_rounds``,
+    ``merged_accepted`` (the merges of each round), ``merged_k`` (the clusters before the first
+    round and after each) and ``merged_mean_rand``; with ``quality=True`` also ``merged_quality``.
     """
+    if merge and consensus is None:
+        raise ValueError("merge=True needs consensus (a threshold or \"best\")")
     if quality and consensus is None:
         raise ValueError("quality=True needs consensus (a threshold or \"best\")")
     if median and consensus is None:
@@ -1582,6 +1779,10 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
             cons.update(median_result(median_refine(eng, cons["voted"] if vote else cons["labels"])))
         if quality:   # of the graph and the partitions alone: no labelings are read
             cons.update(quality_result(eng, cons))
+        if merge:   # last of the refinements; before consensus_scores replaces the labelings
+            cons.update(merge_result(merge_refine(eng, merge_start(cons))))
+            if quality:
+                cons["merged_quality"] = eng.community_quality(cons["merged"])
         ca = None
         if coassoc is not None:   # before consensus_scores replaces the labelings
             ca = coassoc_result(eng, coassoc_nodes(g.n, coassoc, g.labels, seed), g.labels, cons)

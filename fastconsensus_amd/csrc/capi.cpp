@@ -713,6 +713,63 @@ int fc_community_quality(fc_ctx* ctx, int graph, const int32_t* labels, fc_commu
 
 int fc_community_quality_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::ql_ms, ms); }
 
+int fc_community_graph(fc_ctx* ctx, int graph, const int32_t* labels, int64_t capacity, void* a_out, void* b_out,
+                       void* weight_out, void* edges_out, int64_t* npairs_out) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    FC_REQUIRE(labels, FC_EINVAL, "null labels");
+    FC_REQUIRE(npairs_out, FC_EINVAL, "null npairs_out");
+    const uint32_t lim = (uint32_t)c.N;
+    for (int64_t i = 0; i < c.N; ++i)
+        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
+                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    community_graph(c, graph, labels, capacity, (int32_t*)a_out, (int32_t*)b_out, (int64_t*)weight_out,
+                    (int64_t*)edges_out, npairs_out);
+    FC_API_END
+}
+
+int fc_community_graph_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::mg_ms, ms); }
+
+int fc_cluster_coassoc(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const int32_t* a, const int32_t* b,
+                       void* dev_out, fc_cluster_pair_info* info) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    coassoc_state(c);
+    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "pair co-association handles at most 2048 local replicas");
+    FC_REQUIRE(npairs >= 0, FC_EINVAL, "negative pair count");
+    FC_REQUIRE(npairs < ((int64_t)1 << 31), FC_ELIMIT, "pair co-association handles fewer than 2^31 pairs a call");
+    FC_REQUIRE(labels, FC_EINVAL, "null labels");
+    FC_REQUIRE(npairs == 0 || (a && b), FC_EINVAL, "null pair list");
+    FC_REQUIRE(npairs == 0 || dev_out, FC_EINVAL, "null output buffer");
+    const uint32_t lim = (uint32_t)c.N;
+    for (int64_t i = 0; i < c.N; ++i)
+        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
+                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    for (int64_t p = 0; p < npairs; ++p) {
+        FC_REQUIRE((uint32_t)a[p] < lim, FC_EINVAL,
+                   "pair cluster a " + std::to_string(a[p]) + " at index " + std::to_string(p) + " outside [0, n)");
+        FC_REQUIRE((uint32_t)b[p] < lim, FC_EINVAL,
+                   "pair cluster b " + std::to_string(b[p]) + " at index " + std::to_string(p) + " outside [0, n)");
+    }
+    for (double& m : c.mc_ms) m = 0.0;
+    if (npairs == 0) {   // nothing to launch: the cluster count from the host
+        if (info) {
+            std::vector<char> seen((size_t)c.N, 0);
+            int64_t k = 0;
+            for (int64_t i = 0; i < c.N; ++i)
+                if (!seen[labels[i]]) { seen[labels[i]] = 1; ++k; }
+            *info = fc_cluster_pair_info{};
+            info->k = k; info->n_r = c.n_r;
+        }
+    } else
+        cluster_coassoc(c, labels, npairs, a, b, (int64_t*)dev_out, info);
+    FC_API_END
+}
+
+int fc_cluster_coassoc_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::mc_ms, ms); }
+
 int fc_collect_timing(fc_ctx* ctx, fc_stats* st) {
     FC_CTX(ctx)
     FC_API_BEGIN

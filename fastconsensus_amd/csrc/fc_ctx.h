@@ -125,8 +125,8 @@ struct Graph {
     int32_t max_w = 0;              // largest edge weight (unit-weight graphs skip the weight loads)
 };
 
-// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks; vt_ms by vote.h's VoteMarks; ia_ms by affinity.h)
-constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3, VT_PHASES = 4, IA_PHASES = 3, QL_PHASES = 4;
+// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks; vt_ms by vote.h's VoteMarks; ia_ms by affinity.h; mg_ms / mc_ms by merge.h)
+constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3, VT_PHASES = 4, IA_PHASES = 3, QL_PHASES = 4, MG_PHASES = 4, MC_PHASES = 3;
 
 // Every resource goes with the member that holds it (fc_destroy synchronises, then deletes).
 struct Ctx : NoCopy {
@@ -315,6 +315,19 @@ struct Ctx : NoCopy {
     double ql_ms[QL_PHASES] = {};
     DevBuf ql_present, ql_rank, ql_ids, ql_lab, ql_labi, ql_size, ql_nin, ql_nout, ql_vin, ql_vout, ql_vcnt, ql_acc,
         ql_split, ql_psize, ql_rec;
+    // cluster merges (merge.h).  Community graph: the cut edges' keys and weights (unsorted, then
+    // sorted), run lengths and their scan, the pairs before they are handed out (a | b, weight |
+    // edges), counters (it takes its cluster ranks in ql_present / ql_rank / ql_ids / ql_labi)
+    // device time of the last call's phases (timing enabled): labels, emit, sort, pairs
+    double mg_ms[MG_PHASES] = {};
+    DevBuf mg_key, mg_w, mg_cnt, mg_ab, mg_we, mg_ctr;
+    // pair co-association: the pair lists as uploaded (a, then b), cluster ranks (of a, of b, of the
+    // walk side), list-side ranks and pair indices (by pair, then sorted by rank), the listed
+    // clusters with their partner counts and offsets, counters, the sums before they are handed
+    // out, the fallback's lookup threads per pair and their scan
+    // device time of the last call's phases (timing enabled): pairs, count, fallback
+    double mc_ms[MC_PHASES] = {};
+    DevBuf mc_ids, mc_rank, mc_key, mc_idx, mc_qc, mc_qcnt, mc_ctr, mc_out, mc_work;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = env_int("FC_SCORE_SLOW", 0);
     // longest community one wave streams; longer ones go to the fallback
@@ -465,6 +478,11 @@ void item_affinity(Ctx& c, const int32_t* labels, int64_t npairs, const int32_t*
 // quality.h: labels on the host in node order, validated by the caller; any output may be null
 void community_quality(Ctx& c, int graph, const int32_t* labels, fc_community_record* out, int64_t* nin_out,
                        int64_t* nout_out, int32_t* split_out, fc_quality_info* info);
+// merge.h: labels and the pair lists on the host, validated by the caller; npairs >= 1
+void community_graph(Ctx& c, int graph, const int32_t* labels, int64_t capacity, int32_t* a_out, int32_t* b_out,
+                     int64_t* weight_out, int64_t* edges_out, int64_t* npairs_out);
+void cluster_coassoc(Ctx& c, const int32_t* labels, int64_t npairs, const int32_t* a, const int32_t* b, int64_t* dev_out,
+                     fc_cluster_pair_info* info);
 // timing helpers
 int timer_begin(Ctx& c);
 int timer_end(Ctx& c, TimerSlot slot, int begin_ev);   // returns the end event (-1: off)

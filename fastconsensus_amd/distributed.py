@@ -295,13 +295,50 @@ def median_refine_sharded(engine, labels, n_total, device="cuda", max_rounds=64,
                          sum_sq=int(t.item()))
 
 
+def cluster_coassoc_sharded(engine, labels, a, b, device="cuda"):
+    """Engine.cluster_coassoc over every rank's replicas: each rank sums over ITS local labelings,
+    one int64 SUM all-reduce adds the sums, and every rank returns the same dict: x int64[npairs]
+    and slow_lookups (the ranks' sum).  A rank without replicas contributes zeros; `labels` and the
+    pair lists are the same on every rank."""
+    cuda = "cuda:%d" % engine.device
+    npairs = len(np.asarray(a).reshape(-1))
+    buf = torch.zeros(npairs + 1, dtype=torch.int64, device=cuda)   # the sums, then slow_lookups
+    if engine.replica_info()[0] > 0:
+        buf[npairs] = engine.cluster_coassoc(labels, a, b, dev_out=buf)["slow_lookups"]
+    if not str(device).startswith("cuda"):
+        buf = buf.cpu()
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+    out = buf.cpu().numpy()
+    return {"x": out[:npairs].copy(), "slow_lookups": int(out[npairs])}
+
+
+def merge_refine_sharded(engine, labels, n_total, device="cuda", graph="input", max_rounds=64, candidates=None):
+    """core.merge_refine over all n_total replicas of a sharded run: the pair co-association and the
+    cluster consensus through cluster_coassoc_sharded and cluster_consensus_sharded, the replicas'
+    sum_sq added over the ranks; the community graph needs no labelings and is every rank's own.
+    The selection (core.merge_moves) is deterministic on the same integers, so every rank returns
+    the same dict.  `labels` is the same on every rank."""
+    from .core import merge_refine
+    t = torch.zeros(1, dtype=torch.int64, device="cuda:%d" % engine.device if str(device).startswith("cuda") else "cpu")
+    if engine.replica_info()[0] > 0:
+        t[0] = int(np.asarray(engine.score_partitions()["sum_sq"], np.int64).sum())
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return merge_refine(engine, labels, graph=graph, max_rounds=max_rounds, candidates=candidates,
+                        cluster_coassoc=lambda lab, a, b: cluster_coassoc_sharded(engine, lab, a, b, device),
+                        cluster_consensus=lambda lab: cluster_consensus_sharded(engine, lab, n_total, device),
+                        sum_sq=int(t.item()))
+
+
 def _result(res, consensus):
     labels, st = res
     return (labels, st) if consensus is None else (labels, st, st.pop("consensus"))
 
 
 def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, gather=True, out=None,
-                shard_closure=False, out_shared=False, consensus=None, vote=False, median=False, quality=False):
+                shard_closure=False, out_shared=False, consensus=None, vote=False, median=False, quality=False,
+                merge=False):
     """Returns (labels [n_p][N] on rank 0 (None elsewhere), stats dict).  `out`: optional
     C-contiguous int32 host array [n_p][N] that rank 0 downloads into (see Engine.run).
     shard_closure: split the closure's attempts over the ranks (world > 1; same result);
@@ -323,7 +360,13 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     quality: (needs consensus) what the input graph says about the consensus communities
     (Engine.community_quality): the dict gains quality and, for each of voted / median the call
     produced, voted_quality / median_quality.  A property of the graph and the partition alone, so
-    every rank computes it locally and no collective is needed."""
+    every rank computes it locally and no collective is needed.
+    merge: (needs consensus) runs last, on median if it was produced, else on voted, else on the
+    consensus partition: cluster merges towards the median partition of all n_p final partitions
+    (merge_refine_sharded); the dict gains merged, merged_objective, merged_rounds, merged_accepted,
+    merged_k and merged_mean_rand, the same on every rank, and with quality also merged_quality."""
+    if merge and consensus is None:
+        raise ValueError("merge=True needs consensus (a threshold or \"best\")")
     if quality and consensus is None:
         raise ValueError("quality=True needs consensus (a threshold or \"best\")")
     if median and consensus is None:
@@ -343,7 +386,7 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     on_gpu = str(device).startswith("cuda")
     if not on_gpu:
         return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv,
-                             out, shard_closure, out_shared, consensus, vote, median, quality), consensus)
+                             out, shard_closure, out_shared, consensus, vote, median, quality, merge), consensus)
     # engine kernels and torch/RCCL ops on ONE explicit stream: no cross-stream races
     # (torch's default stream is the legacy null stream, which the engine cannot adopt)
     stream = torch.cuda.Stream(device=device)
@@ -352,14 +395,16 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     try:
         with torch.cuda.stream(stream):
             return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1,
-                                 louv, out, shard_closure, out_shared, consensus, vote, median, quality), consensus)
+                                 louv, out, shard_closure, out_shared, consensus, vote, median, quality, merge),
+                           consensus)
     finally:
         stream.synchronize()
         engine.set_stream(None)
 
 
 def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv, out=None,
-          shard_closure=False, out_shared=False, consensus=None, vote=False, median=False, quality=False):
+          shard_closure=False, out_shared=False, consensus=None, vote=False, median=False, quality=False,
+          merge=False):
     mine = r1 - r0
     engine.reset_graph()
     n, _, L = engine.graph_info()
@@ -426,6 +471,11 @@ def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank,
         if quality:
             from .core import quality_result
             st["consensus"].update(quality_result(engine, st["consensus"]))
+        if merge:
+            from .core import merge_result, merge_start
+            st["consensus"].update(merge_result(merge_refine_sharded(engine, merge_start(st["consensus"]), n_p, device)))
+            if quality:
+                st["consensus"]["merged_quality"] = engine.community_quality(st["consensus"]["merged"])
     if gather and world > 1 and out_shared and out is not None:
         # every rank downloads its rows into the shared host array; the barrier orders the
         # writes before rank 0 hands the array back

@@ -27,8 +27,9 @@
  *     next fc_load_graph; fc_consensus_cut reads the hierarchy of the last
  *     fc_consensus_levels, kept until the next fc_load_graph; fc_load_graph drops the
  *     reference labeling of fc_score_set_reference and the labelings.
- *     fc_community_quality depends on the chosen graph and its arguments alone and leaves graph,
- *     labelings, reference, hierarchy and random state as they were.
+ *     fc_community_quality and fc_community_graph depend on the chosen graph and their arguments
+ *     alone and leave graph, labelings, reference, hierarchy and random state as they were;
+ *     fc_cluster_coassoc reads the labelings as well and leaves the same.
  */
 #ifndef FASTCONSENSUS_AMD_H
 #define FASTCONSENSUS_AMD_H
@@ -567,6 +568,61 @@ int fc_community_quality(fc_ctx* ctx, int graph, const int32_t* labels, fc_commu
  * enabled: ms[4] = labels (upload, id ranks, sizes), rows (the CSR pass), fold (per-vertex values to
  * per-cluster sums), components (union-find, split partition, parts, records and totals). */
 int fc_community_quality_timing(fc_ctx* ctx, double* ms);
+
+/* ---- cluster merges: the community graph of a partition, co-association of cluster pairs --- */
+/* The community graph (quotient graph) of a partition P (ids in [0, n), not necessarily dense) on
+ * H = the chosen graph (FC_SCORE_GRAPH_*): the distinct unordered pairs of cluster ids (a < b)
+ * joined by at least one edge of H, ascending by (a, b), so the result is unique; per pair
+ * weight (the sum of w over the joining edges) and edges (their number; weight-0 edges of the
+ * working graph count, as in fc_community_record.in_edges).  Per cluster the weights of its pairs
+ * sum to volume - 2 in_weight of fc_community_quality, and all weights to its cut_weight.  These
+ * are the natural candidates of a merge (DESIGN, "Cluster merges").
+ * labels: host int32[n], P in node order.  a_out, b_out int32[capacity], weight_out, edges_out
+ * int64[capacity]: host memory or device buffers of the context's GPU, any may be NULL.
+ * *npairs_out always receives the number of pairs; with the four outputs NULL the call is the size
+ * query.  The call reads no labelings: it works on a context that has only loaded a graph, and it
+ * is the same on every rank (no collective).  Read-only: the reuse paragraph at the top of this
+ * header holds for this call too.  FC_ESTATE: no graph; FC_EINVAL: labels or npairs_out NULL, an
+ * unknown graph, an id outside [0, n) (the message names the index; checked before any launch), or
+ * an output given with capacity below the count (nothing is written but the count).  Nothing else
+ * is written on error. */
+int fc_community_graph(fc_ctx* ctx, int graph, const int32_t* labels, int64_t capacity, void* a_out, void* b_out,
+                       void* weight_out, void* edges_out, int64_t* npairs_out);
+/* Device time (ms, HIP events) of the phases of the last fc_community_graph made with timing
+ * enabled: ms[4] = labels (upload, id ranks), emit (the pass over the edges), sort (radix sort, run
+ * lengths, prefix sums), pairs (ranks back to ids). */
+int fc_community_graph_timing(fc_ctx* ctx, double* ms);
+
+/* For a partition P and the local labelings, with C_r[k][d] = the number of members of cluster k
+ * that replica r labels d:
+ *   X(a, b) = sum_r sum_d C_r[a][d] * C_r[b][d] = sum over i in a, j in b of coassoc(i, j)
+ * the between-cluster counterpart of fc_cluster_consensus' pairs: X(a, a) is pairs[a], and
+ * X(a, b) / (R s_a s_b) the mean consensus between two clusters.  Joining a != b changes the
+ * median-partition objective F by 2 (2 X(a, b) - R s_a s_b).  Exact integers from the contingency
+ * rows, without the matrix: per pair the larger cluster's rows are listed once for all its
+ * partners and the smaller cluster's members are walked.  A sum over replicas: ranks add theirs
+ * (SUM).  Read-only like fc_cluster_consensus; the reuse paragraph at the top of this header holds
+ * for this call too. */
+typedef struct fc_cluster_pair_info {
+    int64_t k;                /* clusters of P */
+    int64_t listed_clusters;  /* distinct clusters whose (label, count) lists were built */
+    int64_t walked_members;   /* members read on the walk side, summed over the pairs */
+    int64_t slow_lookups;     /* (walk member, replica) pairs the exact fallback answered */
+    int32_t n_r, pad;
+} fc_cluster_pair_info;
+/* out[p] = X(a[p], b[p]) over the LOCAL labelings.  labels: host int32[n], P in node order.  a, b:
+ * host int32[npairs] cluster ids; duplicates, both orders and a[p] == b[p] are allowed; an id in
+ * [0, n) that does not occur in labels gives 0.  dev_out: device int64[npairs].  npairs = 0
+ * launches nothing (the lists and dev_out may then be NULL).  FC_ESTATE: no graph or no
+ * labelings; FC_ELIMIT: more than 2048 local replicas, or npairs >= 2^31; FC_EINVAL: a NULL
+ * pointer, or a cluster or label id outside [0, n) (the message names the index; checked before
+ * any launch).  Nothing is written on error. */
+int fc_cluster_coassoc(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const int32_t* a, const int32_t* b,
+                       void* dev_out, fc_cluster_pair_info* info);
+/* Device time (ms, HIP events) of the phases of the last fc_cluster_coassoc made with timing
+ * enabled: ms[3] = pairs (upload, segments of P, cluster ranks, sides, sort of the pairs), count
+ * (the register-list kernel), fallback (the exact sort-based path). */
+int fc_cluster_coassoc_timing(fc_ctx* ctx, double* ms);
 
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
