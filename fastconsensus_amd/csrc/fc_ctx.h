@@ -399,8 +399,13 @@ struct SweepGeom {
 inline bool cd_leiden_marks(const Ctx& c) {
     return (c.g.max_w > 1 || c.prune_mark == 2) && c.prune && c.prune_mark >= 1;
 }
-// every edge weighs 1 to the decide kernels: LPA ignores the weights, Louvain needs 2M = 2m
-inline bool cd_unit_weights(const Ctx& c, bool louv) { return !louv || (c.g.max_w == 1 && c.g.M2 == 2 * c.g.m); }
+// Every weight of g is 1: the one test behind every kernel variant that skips the weight loads.
+// max_w == 1 alone is not enough: a working graph may hold weight-0 edges beside its 1s (an lpm or
+// infomap step with n_p = 1 keeps agreed edges at 1 and adds closure edges at 0), and each of those
+// lowers M2 below 2 m.
+inline bool unit_weights(const Graph& g) { return g.max_w == 1 && g.M2 == 2 * g.m; }
+// every edge weighs 1 to the decide kernels: LPA ignores the weights, Louvain needs every weight 1
+inline bool cd_unit_weights(const Ctx& c, bool louv) { return !louv || unit_weights(c.g); }
 
 // graph.cpp
 void graph_load(Ctx& c, int64_t n, int64_t m, const int32_t* u, const int32_t* v);

@@ -1357,7 +1357,7 @@ struct LvRun {
         a.nU = nU;
         if (impl) {
             a.rowptr = g.rowptr.as<int64_t>(); a.col = g.col.as<int32_t>();
-            a.w = (info || g.max_w == 1) ? nullptr : g.cw.as<int32_t>();
+            a.w = (info || unit_weights(g)) ? nullptr : g.cw.as<int32_t>();
             a.kv = info ? deg : g.kdeg.as<int64_t>(); a.rep = nullptr;
             a.sv = deg;
         } else {

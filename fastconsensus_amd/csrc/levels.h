@@ -309,7 +309,7 @@ void consensus_levels(Ctx& c, int graph, const int32_t* dev_support, int n_total
     FC_HIP(hipMemsetAsync(jw, 0, sizeof(uint64_t) * ((size_t)nt + 1), c.stream));
     if (m > 0) {
         const size_t lds = sizeof(uint64_t) * ((size_t)nt + 1);
-        if (g.max_w == 1) k_lv_join<true><<<egrid, TB, lds, c.stream>>>(m, eu, ev, nullptr, npos, birth, up, nt, jw);
+        if (unit_weights(g)) k_lv_join<true><<<egrid, TB, lds, c.stream>>>(m, eu, ev, nullptr, npos, birth, up, nt, jw);
         else k_lv_join<false><<<egrid, TB, lds, c.stream>>>(m, eu, ev, g.ew.as<int32_t>(), npos, birth, up, nt, jw);
     }
     std::vector<unsigned long long> hj((size_t)nt + 1);

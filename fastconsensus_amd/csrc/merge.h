@@ -117,7 +117,7 @@ void community_graph(Ctx& c, int graph, const int32_t* labels, int64_t capacity,
     unsigned long long* k2 = k1 + (m + 1);
     int64_t* w2 = w1 + (m + 1);
     if (m > 0) {
-        if (g.max_w == 1 && g.M2 == 2 * m)   // every weight is 1 (a weight-0 edge would lower M2)
+        if (unit_weights(g))
             k_mg_emit<true><<<nblk(m), TB, 0, c.stream>>>(m, g.eu.as<int32_t>(), g.ev.as<int32_t>(), nullptr, labi, k1, w1,
                                                           ctr);
         else

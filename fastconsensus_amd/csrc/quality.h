@@ -270,7 +270,7 @@ void community_quality(Ctx& c, int graph, const int32_t* labels, fc_community_re
             FC_HIP(hipMemsetAsync(vin, 0, sizeof(int64_t) * (size_t)N, c.stream));
             FC_HIP(hipMemsetAsync(vout, 0, sizeof(int64_t) * (size_t)N, c.stream));
             FC_HIP(hipMemsetAsync(vcnt, 0, sizeof(int32_t) * (size_t)N, c.stream));
-        } else if (g.max_w == 1 && g.M2 == 2 * m)   // every weight is 1 (a weight-0 edge would lower M2)
+        } else if (unit_weights(g))
             k_ql_rows<true><<<nblk(N * 16), TB, 0, c.stream>>>(N, g.rowptr.as<int64_t>(), g.col.as<int32_t>(), nullptr,
                                                                labi, npos, nin, nout, vin, vout, vcnt);
         else

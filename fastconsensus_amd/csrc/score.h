@@ -522,7 +522,7 @@ void score_partitions(Ctx& c, int graph, fc_part_score* out) {
     FC_HIP(hipMemsetAsync(inw, 0, sizeof(uint64_t) * n_r, c.stream));
     if (g.m > 0) {
         const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((g.m + 255) / 256, SC_GRID)), (n_r + 63) / 64);
-        if (g.max_w == 1)
+        if (unit_weights(g))
             k_sc_edges<true><<<grid, TB, 0, c.stream>>>(g.m, g.eu.as<int32_t>(), g.ev.as<int32_t>(), nullptr,
                                                          c.labT.as<int32_t>(), c.ldT, n_r, inw);
         else

@@ -7,16 +7,23 @@ and the co-association histogram pass 2^32 -- tests/test_analysis_mid_cases.py c
 that the inputs do reach each of these.  Integers compare with np.array_equal; the floats of the
 scores keep tests/test_gpu_score.py's bounds.
 
-Not reached here: the 128-bit carry of tot_sq (needs 2M > 2^32) and a co-association matrix of more
-than 2^31 entries (a 9 GB buffer on a shared card); the largest matrix is 4,099 x 4,001."""
+fc_community_quality takes the five partitions of tests/quality_mid.py on the same engine: more
+clusters than k_ql_records' shards cover in one trip, a one-component cluster of 349,029 nodes, a
+cluster of 732 parts (tests/test_quality_mid_cases.py checks these without a GPU).
+
+Not reached here: a co-association matrix of more than 2^31 entries (a 9 GB buffer on a shared
+card); the largest matrix is 4,099 x 4,001.  The 128-bit carry of tot_sq needs 2M > 2^32:
+tests/test_gpu_wide_weight_analysis.py reaches it on a 3,000-node graph."""
 import numpy as np
 import pytest
 
 from tests import analysis_mid as am
 from tests import cluster_consensus_ref as ccr
 from tests import consensus_levels_ref as lref
+from tests import quality_mid as qm
 from tests import score_ref
 from tests import vote_ref as vr
+from tests.test_gpu_community_quality import same as same_quality
 from tests.test_gpu_consensus import same as same_partition
 from tests.test_gpu_consensus_levels import same_record
 
@@ -240,3 +247,40 @@ def test_coassociation_matrix(mid, case):
     wrong = np.argwhere(got.cpu().numpy() != case["ca_matrix"])
     assert not len(wrong), (len(wrong), wrong[:5])
     assert len(np.unique(case["ca_matrix"])) > 10
+
+
+# ------------------------------------------------------------------ 7. community quality
+@pytest.fixture(scope="module")
+def quality(case):
+    q = qm.case()                           # the five references here, so that no test's time holds one
+    yield q
+    qm.case.cache_clear()
+
+
+@pytest.mark.parametrize("which", qm.NAMES)
+def test_community_quality(mid, quality, fcmod, which):
+    P, ref = quality[which]
+    same_quality(mid.eng.community_quality(P), ref)
+    assert np.array_equal(fcmod.split_disconnected(mid.eng, P), ref["split"])
+
+
+def test_community_quality_fold_waves(fcmod, case, quality):
+    """k_ql_fold retires one distinct cluster of a wave's 64 storage slots per turn.  The default
+    storage order comes from an ordering pass and cannot be read back, so this engine keeps the
+    identity storage (FC_OPT_STORE = 0): slot i holds internal vertex i and node_map() tells which
+    nodes share a wave.  Then the fine row has waves of 64 distinct clusters (64 turns, no fold) and
+    the coarse row waves that lie wholly inside one cluster (one turn, every fold over 64 lanes).
+    No wave lies wholly inside C: under a random numbering that needs 64 of its 16 % in a row."""
+    with fcmod.Engine(seed=SEED) as eng:
+        eng.set_option("store", 0)
+        eng.load_graph(case["n"], case["u"], case["v"])
+        order = np.argsort(eng.node_map())                   # order[i] = the node of internal vertex i
+        fine = qm.wave_clusters(order, quality["fine"][0])
+        coarse = qm.wave_clusters(order, quality["coarse"][0])
+        in_c = (case["part"] == case["ids_cab"][0])[order[:len(order) // 64 * 64]].reshape(-1, 64).all(1)
+        print("waves of 64 distinct clusters (fine row): %d; waves inside one cluster (coarse row): %d; waves inside C: %d"
+              % ((fine == 64).sum(), (coarse == 1).sum(), in_c.sum()))
+        assert (fine == 64).any() and (coarse == 1).any()
+        for which in ("fine", "coarse", "part"):
+            P, ref = quality[which]
+            same_quality(eng.community_quality(P), ref)

@@ -34,13 +34,13 @@ from oracle import oracle as orc
 from tests.test_gpu_parity import TAILS, _engine, _heavy_graph
 from tests.test_gpu_rl_decide_widths import BLOCK, BLOCKS, BOUNDARY_DEGREES, EDGES, LAYOUTS, N, PER_DEGREE
 from tests.twin_graph import internal_graph
+from tests.weighted_graph import weighted_engine
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 SEED = 131
-DELTA = 0.02
 ITERATION = 3
 I31 = (1 << 31) - 1
 GAIN_LIMIT = 4.0e18       # cd.hip: max k_v * 2M below it, or exact int64 gains are refused
@@ -108,29 +108,16 @@ class Weighted:
     def __init__(self, fcmod, n, edges, blocks, k, w_max, out_levels=OUT_LEVELS, block_k=None):
         """block_k: the k of every block where the blocks differ (at most k)."""
         self.n, self.n_p = n, 1 << k            # n_p_total of the fc_cd calls: an in-block level
-        eng = self.eng = fcmod.Engine(seed=SEED)
-        eng.load_graph(n, edges[:, 0], edges[:, 1])
-        u, v, w, _ = eng.get_graph()
-        assert (w == 1).all()
-        deg = np.bincount(np.concatenate([u, v]), minlength=n)
-        # the internal canonical edge list: the index space of the partial buffer
-        sigma = eng.node_map()
-        lo, hi = np.minimum(sigma[u], sigma[v]), np.maximum(sigma[u], sigma[v])
-        o = np.lexsort((hi, lo))
-        weights = level_weights(blocks[u[o]] == blocks[v[o]], k, w_max, out_levels,
-                                None if block_k is None else np.asarray(block_k)[blocks[u[o]]])
-        part = torch.from_numpy(weights).to("cuda")
-        eng.consensus_apply(1, self.n_p, 0.0, DELTA, part)      # tau 0: every edge kept, weight part[e]
-        eng.closure_set_pairs(np.empty((0, 2), np.int32), 0)
-        eng.closure_apply(1, self.n_p, DELTA, None, 0)
-        self.g_int, self.sigma = internal_graph(eng, n)
+        # weighted_engine asserts that the weights were written edge for edge and that every row
+        # kept its degree (the boundary-degree probes survive)
+        self.eng, sigma, (u2, v2, w2) = weighted_engine(
+            fcmod, n, edges,
+            lambda u, v: level_weights(blocks[u] == blocks[v], k, w_max, out_levels,
+                                       None if block_k is None else np.asarray(block_k)[blocks[u]]),
+            SEED, n_p=self.n_p)
+        self.g_int, self.sigma = internal_graph(self.eng, n)
         np.testing.assert_array_equal(self.sigma, sigma)
-        np.testing.assert_array_equal(self.g_int.u, lo[o])
-        np.testing.assert_array_equal(self.g_int.v, hi[o])
-        np.testing.assert_array_equal(self.g_int.w, weights)    # the weights written, edge for edge
-        u2, v2, w2, _ = eng.get_graph()
         self.deg = np.bincount(np.concatenate([u2, v2]), minlength=n)
-        np.testing.assert_array_equal(self.deg, deg)            # the boundary-degree probes survive
         self.max_w = int(w2.max())
         self.wbits = self.max_w.bit_length()
         self.m2 = 2 * int(w2.astype(np.int64).sum())
