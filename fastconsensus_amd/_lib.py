@@ -39,6 +39,7 @@ SYMBOLS = [
     "fc_item_affinity", "fc_item_affinity_timing",
     "fc_community_quality", "fc_community_quality_timing",
     "fc_community_graph", "fc_community_graph_timing", "fc_cluster_coassoc", "fc_cluster_coassoc_timing",
+    "fc_cluster_match", "fc_cluster_match_timing",
 ]
 FC_SCORE_REF = -1
 SCORE_GRAPHS = {"input": 0, "working": 1}
@@ -154,6 +155,18 @@ class ClusterPairInfo(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
 
+class MatchInfo(ctypes.Structure):
+    """fc_match_info"""
+    _fields_ = [
+        ("k", ctypes.c_int64), ("max_size", ctypes.c_int64), ("singletons", ctypes.c_int64),
+        ("perfect", ctypes.c_int64), ("inter_total", ctypes.c_int64), ("slow_members", ctypes.c_int64),
+        ("n_r", ctypes.c_int32), ("pad", ctypes.c_int32),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
 class QualityInfo(ctypes.Structure):
     """fc_quality_info"""
     _fields_ = [
@@ -256,6 +269,9 @@ def load():
     # labels (host), npairs, a, b (host), dev_out, fc_cluster_pair_info
     L.fc_cluster_coassoc.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     L.fc_cluster_coassoc_timing.argtypes = [vp, P(dbl)]
+    # labels, other (host; other or NULL), ld, ids_out, size_out (host or NULL), dev_inter, dev_csize, fc_match_info
+    L.fc_cluster_match.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    L.fc_cluster_match_timing.argtypes = [vp, P(dbl)]
     _lib = L
     return L
 

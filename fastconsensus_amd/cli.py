@@ -37,6 +37,11 @@ consensus partition: cluster merges towards the median partition (``merge_refine
 row per round, no header: round, objective, k, pairs, proposed, accepted (round 0: the objective
 and the clusters before the first round, then zeros).  With ``--quality`` it also writes
 ``merged_quality.tsv`` (of ``merge_membership``), ``quality.tsv``'s columns.
+``--match`` (with ``--consensus`` or ``--consensus-levels``) looks for every consensus community in
+the n_p partitions (``Engine.cluster_match``: its best match by Jaccard index) and adds
+``consensus_t.../cluster_match.tsv``: one row per community, no header: ``community+1``, size,
+stability (the mean Jaccard index, ``%.17g``), recovered, dissolved (the partitions with J >= 3/4,
+with J <= 1/2).
 """
 import argparse
 import os
@@ -97,6 +102,8 @@ def build_parser():
     p.add_argument('--quality', action='store_true', help=argparse.SUPPRESS)
     # extension: cluster merges of the consensus partition towards the median partition
     p.add_argument('--merge', action='store_true', help=argparse.SUPPRESS)
+    # extension: cluster-wise Jaccard stability of the consensus partition over the partitions
+    p.add_argument('--match', action='store_true', help=argparse.SUPPRESS)
     return p
 
 
@@ -220,6 +227,17 @@ def write_merge(args, node_labels, mg, root='.'):
             f.write("%d\t%d\t%d\t%d\t%d\t%d\n" % ((r,) + row))
 
 
+def write_match(args, cm, root='.'):
+    """consensus_t.../cluster_match.tsv (community+1, size, stability, recovered, dissolved; one row
+    per community in id order, no header, the float as %.17g).  cm: the dict of Engine.cluster_match."""
+    d = os.path.join(root, 'consensus_' + output_dirs(args)[0][len('out_partitions_'):])
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(d, 'cluster_match.tsv'), 'w') as f:
+        for row in zip(cm["ids"].tolist(), cm["size"].tolist(), cm["stability"].tolist(), cm["recovered"].tolist(),
+                       cm["dissolved"].tolist()):
+            f.write("%d\t%d\t%.17g\t%d\t%d\n" % ((row[0] + 1,) + row[1:]))
+
+
 def write_quality(args, node_labels, q, name='quality.tsv', split=True, root='.'):
     """consensus_t.../`name` (community+1, size, in_weight, cut, volume, conductance, density,
     components, largest_component; one row per community in id order, no header, floats as %.17g)
@@ -267,7 +285,9 @@ def main(argv=None):
         raise SystemExit("--quality needs --consensus or --consensus-levels")
     if args.merge and args.consensus is None and not args.consensus_levels:
         raise SystemExit("--merge needs --consensus or --consensus-levels")
-    cons = ca = cc = vt = md = ql = mg = None
+    if args.match and args.consensus is None and not args.consensus_levels:
+        raise SystemExit("--match needs --consensus or --consensus-levels")
+    cons = ca = cc = vt = md = ql = mg = cm = None
     g = IdGraph.from_edgelist_file(args.f)
     if args.coassoc is not None and not 0 <= args.coassoc <= g.n:
         raise SystemExit("--coassoc must lie in [0, %d], the number of nodes" % g.n)
@@ -302,6 +322,8 @@ def main(argv=None):
                 mg = merge_refine(eng, start)
                 if args.quality:
                     ql["merged_quality.tsv"] = eng.community_quality(mg["labels"])
+            if args.match:
+                cm = eng.cluster_match(cons["labels"])
             if args.coassoc is not None:
                 ids = coassoc_nodes(g.n, args.coassoc, g.labels, args.seed)
                 ca = (ids, eng.coassociation(ids).cpu().numpy())
@@ -321,6 +343,8 @@ def main(argv=None):
         write_median(args, g.labels, md)
     if mg is not None:
         write_merge(args, g.labels, mg)
+    if cm is not None:
+        write_match(args, cm)
     for name, q in (ql or {}).items():
         write_quality(args, g.labels, q, name=name, split=name == 'quality.tsv')
     if ca is not None:

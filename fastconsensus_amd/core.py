@@ -800,6 +800,60 @@ class Engine:
         (set_timing): pairs, count, fallback."""
         return self._phase_timing(self._L.fc_cluster_coassoc_timing, ("pairs", "count", "fallback"))
 
+    # -- cluster-wise Jaccard best match (fc_cluster_match) ---------------------------------
+    def _match_out(self, dev_out, rows, k, name):
+        """An int32 device tensor [>= rows, ld >= k] for one of cluster_match's tables: `dev_out`
+        when given (checked), else a new [rows, k]."""
+        import torch
+        if dev_out is None:
+            return torch.empty((max(rows, 1), max(k, 1)), dtype=torch.int32, device="cuda:%d" % self.device)
+        if dev_out.dtype != torch_int32() or dev_out.dim() != 2 or not dev_out.is_contiguous() or \
+                dev_out.shape[0] < rows or dev_out.shape[1] < k:
+            raise ValueError("%s must be a contiguous int32 tensor [>= %d, >= %d]" % (name, rows, k))
+        return dev_out
+
+    def cluster_match(self, part, other=None, dev_inter=None, dev_csize=None):
+        """The best match, by Jaccard index, of every cluster of the partition `part` ([n] in node
+        order, integer ids in [0, n), not necessarily dense) in every local labeling -- or, with
+        `other` ([n] in node order, ids in [0, n)), in that one labeling alone, which needs no
+        labelings and leaves them untouched (found against planted, one cut against another).
+        For cluster k (size s) and row r the community d of r with the largest
+        C / (s + t - C), C = |k and d|, t = |d|, chosen on integers (cross-multiplied; among
+        equal fractions the larger C), so the pair (C, t) is unique.  Returns a dict: ids int32[K]
+        (the distinct ids, ascending) and size int64[K]; inter and csize int32[rows, K] (C and t
+        of the match; rows = n_r, or 1 with `other`); the fc_match_info fields (k, max_size,
+        singletons, perfect, inter_total, slow_members, n_r); and the module-level functions of
+        those integers: jaccard and f1 float64[rows, K], stability float64[K] (Hennig's cluster-wise
+        stability: the mean Jaccard over the rows), recovered and dissolved int64[K] (rows with
+        J >= 3/4, with J <= 1/2).  `dev_inter` / `dev_csize`: contiguous int32 device tensors
+        [>= rows, ld >= K] of one shape to write into (row r's first K entries; the rest is left
+        alone); distributed.cluster_match_sharded gathers the ranks' rows."""
+        lab = self._vote_labels(part)
+        oth = None if other is None else self._vote_labels(other)
+        rows = 1 if other is not None else self.replica_info()[0]
+        k = len(np.unique(lab))
+        dev_inter = self._match_out(dev_inter, rows, k, "dev_inter")
+        dev_csize = self._match_out(dev_csize, rows, k, "dev_csize")
+        if dev_inter.shape[1] != dev_csize.shape[1]:
+            raise ValueError("dev_inter and dev_csize must have one row length")
+        n = self.n
+        ids = np.empty(max(n, 1), np.int32)
+        size = np.empty(max(n, 1), np.int64)
+        info = _lib.MatchInfo()
+        check(self._L.fc_cluster_match(self._ctx, ptr(lab), ptr(oth), dev_inter.shape[1], ptr(ids), ptr(size),
+                                       self._dev(dev_inter), self._dev(dev_csize), ctypes.addressof(info)))
+        k = info.k
+        out = {"ids": ids[:k].copy(), "size": size[:k].copy(), "inter": dev_inter[:info.n_r, :k].cpu().numpy(),
+               "csize": dev_csize[:info.n_r, :k].cpu().numpy()}
+        out.update(info.as_dict())
+        out.update(match_summary(out["inter"], out["size"], out["csize"]))
+        return out
+
+    def cluster_match_timing(self):
+        """Device milliseconds of the phases of the last cluster_match made with timing on
+        (set_timing): segments, sizes, match, fallback."""
+        return self._phase_timing(self._L.fc_cluster_match_timing, ("segments", "sizes", "match", "fallback"))
+
     def nmi_matrix(self):
         """Symmetric [n_r, n_r] float64 NMI between the local replicas (unit diagonal)."""
         return self._pair_matrices()[0]
@@ -858,6 +912,73 @@ def cluster_result(eng, labels):
     """What fast_consensus(cluster_consensus=True) adds to the `consensus` dict."""
     cc = eng.cluster_consensus(labels)
     return {k: cc[k] for k in ("cluster_consensus", "item_consensus", "cluster_pairs", "item_pairs")}
+
+
+def _match_ints(inter, size, csize):
+    """inter, csize [..., K] and size [K] as int64, and the union size + csize - inter"""
+    inter, size, csize = np.asarray(inter, np.int64), np.asarray(size, np.int64), np.asarray(csize, np.int64)
+    return inter, size, csize, size + csize - inter
+
+
+def jaccard(inter, size, csize):
+    """inter / (size + csize - inter), float64: the Jaccard index of every best match from the
+    integers of Engine.cluster_match (inter, csize [rows, K] or [K]; size [K])."""
+    inter, _, _, union = _match_ints(inter, size, csize)
+    return inter / union
+
+
+def match_f1(inter, size, csize):
+    """2 inter / (size + csize), float64: the F1 of every best match (precision inter / csize,
+    recall inter / size); 2 J / (1 + J), so the match of largest J is the match of largest F1."""
+    inter, size, csize, _ = _match_ints(inter, size, csize)
+    return 2 * inter / (size + csize)
+
+
+def cluster_stability(inter, size, csize):
+    """Hennig's cluster-wise stability, float64 [K]: the mean over the rows of jaccard."""
+    return np.atleast_2d(jaccard(inter, size, csize)).mean(axis=0)
+
+
+def recovered(inter, size, csize, num=3, den=4):
+    """int64 [K]: the rows in which the cluster is recovered, J >= num / den, decided on integers
+    as den * inter >= num * union (Hennig's 0.75 by default)."""
+    inter, _, _, union = _match_ints(inter, size, csize)
+    return np.atleast_2d(den * inter >= num * union).sum(axis=0).astype(np.int64)
+
+
+def dissolved(inter, size, csize, num=1, den=2):
+    """int64 [K]: the rows in which the cluster is dissolved, J <= num / den, decided on integers
+    as den * inter <= num * union (Hennig's 0.5 by default)."""
+    inter, _, _, union = _match_ints(inter, size, csize)
+    return np.atleast_2d(den * inter <= num * union).sum(axis=0).astype(np.int64)
+
+
+def match_summary(inter, size, csize):
+    """The derived arrays of Engine.cluster_match: jaccard, f1, stability, recovered, dissolved."""
+    return {"jaccard": jaccard(inter, size, csize), "f1": match_f1(inter, size, csize),
+            "stability": cluster_stability(inter, size, csize), "recovered": recovered(inter, size, csize),
+            "dissolved": dissolved(inter, size, csize)}
+
+
+def match_result(eng, labels):
+    """What fast_consensus(match=True) adds to the `consensus` dict.  The keys carry the call's name:
+    the dict's `stability` is the per-node value of consensus_partition."""
+    cm = eng.cluster_match(labels)
+    return {"match_inter": cm["inter"], "match_csize": cm["csize"], "match_stability": cm["stability"],
+            "match_recovered": cm["recovered"], "match_dissolved": cm["dissolved"]}
+
+
+def truth_match(eng, truth, labels):
+    """The per-community evaluation of the partition `labels` against the planted partition `truth`
+    (both [n] in node order; truth's ids are arbitrary integers): Engine.cluster_match with P = the
+    planted partition and `labels` as the one row.  ids (truth's own ids, ascending), size, inter,
+    csize, jaccard, f1 [K] and mean_f1."""
+    ids, dense = np.unique(np.asarray(truth), return_inverse=True)
+    cm = eng.cluster_match(dense.reshape(-1).astype(np.int32), other=labels)
+    out = {"ids": ids, "size": cm["size"]}
+    out.update({k: cm[k][0] for k in ("inter", "csize", "jaccard", "f1")})
+    out["mean_f1"] = float(out["f1"].mean())
+    return out
 
 
 def conductance(cut, volume, total_degree):
@@ -1659,7 +1780,8 @@ def relabel_for(algorithm):
 
 def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, seed=None, device=0,
                    return_stats=False, rule="fast_consensus", scores=False, truth=None, consensus=None,
-                   coassoc=None, cluster_consensus=False, vote=False, median=False, quality=False, merge=False):
+                   coassoc=None, cluster_consensus=False, vote=False, median=False, quality=False, merge=False,
+                   match=False):
     """Drop-in for fast_consensus.py:129 ``fast_consensus(G, algorithm, n_p, thresh, delta)``.
 
     G: an undirected networkx Graph (weights are ignored: the reference resets them to 1,
@@ -1732,7 +1854,18 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     per node), ``merged_objective`` (F before the first round and after each), ``merged_rounds``,
     ``merged_accepted`` (the merges of each round), ``merged_k`` (the clusters before the first
     round and after each) and ``merged_mean_rand``; with ``quality=True`` also ``merged_quality``.
+
+    ``match=True`` (needs ``consensus``) asks of every consensus community whether the n_p
+    partitions contain it as a community (``Engine.cluster_match``: its best match by Jaccard index
+    in each partition) and adds to the ``consensus`` dict ``match_inter`` and ``match_csize`` (int32
+    [n_p, K]: the overlap with, and the size of, the matched community), ``match_stability``
+    (float64 [K]: Hennig's cluster-wise stability, the mean Jaccard index), ``match_recovered`` and
+    ``match_dissolved`` (int64 [K]: the partitions with J >= 3/4, with J <= 1/2).  With ``truth`` it
+    also adds ``truth_match``: the planted communities against the consensus partition (``ids``,
+    ``size``, ``inter``, ``csize``, ``jaccard``, ``f1`` per planted community, and ``mean_f1``).
     """
+    if match and consensus is None:
+        raise ValueError("match=True needs consensus (a threshold or \"best\")")
     if merge and consensus is None:
         raise ValueError("merge=True needs consensus (a threshold or \"best\")")
     if quality and consensus is None:
@@ -1783,6 +1916,10 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
             cons.update(merge_result(merge_refine(eng, merge_start(cons))))
             if quality:
                 cons["merged_quality"] = eng.community_quality(cons["merged"])
+        if match:   # before consensus_scores replaces the labelings
+            cons.update(match_result(eng, cons["labels"]))
+            if tr is not None:
+                cons["truth_match"] = truth_match(eng, tr, cons["labels"])
         ca = None
         if coassoc is not None:   # before consensus_scores replaces the labelings
             ca = coassoc_result(eng, coassoc_nodes(g.n, coassoc, g.labels, seed), g.labels, cons)

@@ -103,7 +103,7 @@ struct fc_ctx {
     Ctx& c = (ctx)->c;                                           \
     bind(c);
 
-// the fc_*_timing getters: the device time of the last call's phases (Ctx::cp_ms / lv_ms / ca_ms / cc_ms)
+// the fc_*_timing getters: the device time of the last call's phases (Ctx::cp_ms / lv_ms / ca_ms / cc_ms / cm_ms)
 template <int N> static int phase_timing(fc_ctx* ctx, double (Ctx::*src)[N], double* ms) {
     FC_CTX(ctx)
     FC_API_BEGIN
@@ -769,6 +769,33 @@ int fc_cluster_coassoc(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const
 }
 
 int fc_cluster_coassoc_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::mc_ms, ms); }
+
+// cluster match: every id of one host array, before anything is launched
+static void match_ids(const Ctx& c, const char* what, const int32_t* ids) {
+    const uint32_t lim = (uint32_t)c.N;
+    for (int64_t i = 0; i < c.N; ++i)
+        FC_REQUIRE((uint32_t)ids[i] < lim, FC_EINVAL,
+                   std::string(what) + ": id " + std::to_string(ids[i]) + " at index " + std::to_string(i) +
+                       " outside [0, n)");
+}
+
+int fc_cluster_match(fc_ctx* ctx, const int32_t* labels, const int32_t* other, int64_t ld, int32_t* ids_out,
+                     int64_t* size_out, void* dev_inter, void* dev_csize, fc_match_info* info) {
+    FC_CTX(ctx)
+    FC_API_BEGIN
+    FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
+    if (!other) {
+        FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings: run fc_run, fc_cd or fc_set_labels first, or pass `other`");
+        FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "the cluster match handles at most 2048 local replicas");
+    }
+    FC_REQUIRE(labels, FC_EINVAL, "null labels");
+    match_ids(c, "labels", labels);
+    if (other) match_ids(c, "other", other);
+    cluster_match(c, labels, other, ld, ids_out, size_out, (int32_t*)dev_inter, (int32_t*)dev_csize, info);
+    FC_API_END
+}
+
+int fc_cluster_match_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::cm_ms, ms); }
 
 int fc_collect_timing(fc_ctx* ctx, fc_stats* st) {
     FC_CTX(ctx)

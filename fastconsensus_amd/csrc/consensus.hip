@@ -908,3 +908,4 @@ void closure_apply(Ctx& c, int algo, int n_p, const int32_t* counts, int iterati
 #include "vote.h"         // plurality vote on a partition (fc_vote_map / fc_vote_count / fc_vote)
 #include "affinity.h"     // a node's co-association summed over any cluster (fc_item_affinity)
 #include "merge.h"        // community graph and pair co-association of a partition (fc_community_graph / fc_cluster_coassoc)
+#include "match.h"        // cluster-wise Jaccard best match of a partition (fc_cluster_match)

@@ -125,8 +125,8 @@ struct Graph {
     int32_t max_w = 0;              // largest edge weight (unit-weight graphs skip the weight loads)
 };
 
-// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks; vt_ms by vote.h's VoteMarks; ia_ms by affinity.h; mg_ms / mc_ms by merge.h)
-constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3, VT_PHASES = 4, IA_PHASES = 3, QL_PHASES = 4, MG_PHASES = 4, MC_PHASES = 3;
+// timed phases of one analysis call (Ctx::cp_ms / lv_ms / ca_ms / cc_ms, written by analysis.h's PhaseMarks; vt_ms by vote.h's VoteMarks; ia_ms by affinity.h; mg_ms / mc_ms by merge.h; cm_ms by match.h)
+constexpr int CP_PHASES = 5, LV_PHASES = 4, CA_PHASES = 2, CC_PHASES = 3, VT_PHASES = 4, IA_PHASES = 3, QL_PHASES = 4, MG_PHASES = 4, MC_PHASES = 3, CM_PHASES = 4;
 
 // Every resource goes with the member that holds it (fc_destroy synchronises, then deletes).
 struct Ctx : NoCopy {
@@ -328,6 +328,12 @@ struct Ctx : NoCopy {
     // device time of the last call's phases (timing enabled): pairs, count, fallback
     double mc_ms[MC_PHASES] = {};
     DevBuf mc_ids, mc_rank, mc_key, mc_idx, mc_qc, mc_qcnt, mc_ctr, mc_out, mc_work;
+    // cluster match (match.h): `other` as a one-column labT, the community sizes of every replica
+    // ([N][ldT] by label), the two tables when the caller gives none, the fallback's best cell per
+    // (entry, lane), the two totals (P's slot-order row and the emit's vertex values: cc_row, cc_fv1)
+    // device time of the last call's phases (timing enabled): segments, sizes, match, fallback
+    double cm_ms[CM_PHASES] = {};
+    DevBuf cm_col, cm_csz, cm_inter, cm_csize, cm_best, cm_tot;
     // FC_SCORE_SLOW=1: every (community, replica) through the exact fallback (debug switch; same integers)
     int score_slow = env_int("FC_SCORE_SLOW", 0);
     // longest community one wave streams; longer ones go to the fallback
@@ -488,6 +494,9 @@ void community_graph(Ctx& c, int graph, const int32_t* labels, int64_t capacity,
                      int64_t* weight_out, int64_t* edges_out, int64_t* npairs_out);
 void cluster_coassoc(Ctx& c, const int32_t* labels, int64_t npairs, const int32_t* a, const int32_t* b, int64_t* dev_out,
                      fc_cluster_pair_info* info);
+// match.h: labels and other (or null: the local labelings) on the host, validated by the caller
+void cluster_match(Ctx& c, const int32_t* labels, const int32_t* other, int64_t ld, int32_t* ids_out, int64_t* size_out,
+                   int32_t* dev_inter, int32_t* dev_csize, fc_match_info* info);
 // timing helpers
 int timer_begin(Ctx& c);
 int timer_end(Ctx& c, TimerSlot slot, int begin_ev);   // returns the end event (-1: off)

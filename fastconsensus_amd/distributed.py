@@ -331,6 +331,51 @@ def merge_refine_sharded(engine, labels, n_total, device="cuda", graph="input", 
                         sum_sq=int(t.item()))
 
 
+def cluster_match_sharded(engine, labels, n_total, device="cuda"):
+    """Engine.cluster_match of the partition `labels` against all n_total replicas of a sharded run.
+    A row of the two tables depends on its own replica alone, so nothing is reduced: each rank
+    computes ITS rows, the int32 [n_r, K] blocks are all-gathered in rank order -- the global
+    replica order of run_sharded's contiguous shards; a count exchange, then the blocks padded to
+    the largest -- and every rank derives the same summary from the same [n_total, K] integers.
+    Returns the dict of Engine.cluster_match, the same on every rank and identical to one rank
+    holding every replica, with perfect, inter_total and slow_members summed over the ranks and
+    n_r = n_total.  A rank without replicas contributes no rows; `labels` is the same on every rank."""
+    from .core import match_summary
+    labels = np.asarray(labels)
+    cuda = "cuda:%d" % engine.device
+    comm = cuda if str(device).startswith("cuda") else "cpu"
+    ids, size = np.unique(labels, return_counts=True)
+    k = len(ids)
+    n_r = engine.replica_info()[0]
+    both = torch.zeros((2, 0, k), dtype=torch.int32, device=cuda)   # inter, then csize
+    sums = [n_r, 0, 0, 0]
+    if n_r > 0:
+        both = torch.empty((2, n_r, k), dtype=torch.int32, device=cuda)
+        cm = engine.cluster_match(labels, dev_inter=both[0], dev_csize=both[1])
+        sums = [n_r, cm["perfect"], cm["inter_total"], cm["slow_members"]]
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        world = dist.get_world_size()
+        cnt = torch.tensor(sums, dtype=torch.int64, device=comm)
+        cnts = [torch.empty_like(cnt) for _ in range(world)]
+        dist.all_gather(cnts, cnt)
+        cnts = torch.stack(cnts).cpu()
+        buf = torch.zeros((2, max(int(cnts[:, 0].max()), 1), k), dtype=torch.int32, device=comm)
+        buf[:, :n_r].copy_(both)
+        bufs = [torch.empty_like(buf) for _ in range(world)]
+        dist.all_gather(bufs, buf)
+        both = torch.cat([bufs[g][:, :int(cnts[g, 0])] for g in range(world)], dim=1)
+        sums = cnts.sum(0).tolist()
+    if both.shape[1] != int(n_total):
+        raise ValueError("the ranks hold %d labelings, n_total = %d" % (both.shape[1], n_total))
+    inter, csize = both[0].cpu().numpy(), both[1].cpu().numpy()
+    size = size.astype(np.int64)
+    out = {"ids": ids.astype(np.int32), "size": size, "inter": inter, "csize": csize, "k": k,
+           "max_size": int(size.max()), "singletons": int((size == 1).sum()), "perfect": int(sums[1]),
+           "inter_total": int(sums[2]), "slow_members": int(sums[3]), "n_r": int(n_total)}
+    out.update(match_summary(inter, size, csize))
+    return out
+
+
 def _result(res, consensus):
     labels, st = res
     return (labels, st) if consensus is None else (labels, st, st.pop("consensus"))
@@ -338,7 +383,7 @@ def _result(res, consensus):
 
 def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, gather=True, out=None,
                 shard_closure=False, out_shared=False, consensus=None, vote=False, median=False, quality=False,
-                merge=False):
+                merge=False, match=False):
     """Returns (labels [n_p][N] on rank 0 (None elsewhere), stats dict).  `out`: optional
     C-contiguous int32 host array [n_p][N] that rank 0 downloads into (see Engine.run).
     shard_closure: split the closure's attempts over the ranks (world > 1; same result);
@@ -364,7 +409,12 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     merge: (needs consensus) runs last, on median if it was produced, else on voted, else on the
     consensus partition: cluster merges towards the median partition of all n_p final partitions
     (merge_refine_sharded); the dict gains merged, merged_objective, merged_rounds, merged_accepted,
-    merged_k and merged_mean_rand, the same on every rank, and with quality also merged_quality."""
+    merged_k and merged_mean_rand, the same on every rank, and with quality also merged_quality.
+    match: (needs consensus) the best match, by Jaccard index, of every consensus community in all
+    n_p final partitions (cluster_match_sharded); the dict gains match_inter, match_csize,
+    match_stability, match_recovered and match_dissolved, the same on every rank."""
+    if match and consensus is None:
+        raise ValueError("match=True needs consensus (a threshold or \"best\")")
     if merge and consensus is None:
         raise ValueError("merge=True needs consensus (a threshold or \"best\")")
     if quality and consensus is None:
@@ -386,7 +436,7 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     on_gpu = str(device).startswith("cuda")
     if not on_gpu:
         return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv,
-                             out, shard_closure, out_shared, consensus, vote, median, quality, merge), consensus)
+                             out, shard_closure, out_shared, consensus, vote, median, quality, merge, match), consensus)
     # engine kernels and torch/RCCL ops on ONE explicit stream: no cross-stream races
     # (torch's default stream is the legacy null stream, which the engine cannot adopt)
     stream = torch.cuda.Stream(device=device)
@@ -395,7 +445,7 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     try:
         with torch.cuda.stream(stream):
             return _result(_loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1,
-                                 louv, out, shard_closure, out_shared, consensus, vote, median, quality, merge),
+                                 louv, out, shard_closure, out_shared, consensus, vote, median, quality, merge, match),
                            consensus)
     finally:
         stream.synchronize()
@@ -404,7 +454,7 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
 
 def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank, r0, r1, louv, out=None,
           shard_closure=False, out_shared=False, consensus=None, vote=False, median=False, quality=False,
-          merge=False):
+          merge=False, match=False):
     mine = r1 - r0
     engine.reset_graph()
     n, _, L = engine.graph_info()
@@ -476,6 +526,11 @@ def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank,
             st["consensus"].update(merge_result(merge_refine_sharded(engine, merge_start(st["consensus"]), n_p, device)))
             if quality:
                 st["consensus"]["merged_quality"] = engine.community_quality(st["consensus"]["merged"])
+        if match:
+            cm = cluster_match_sharded(engine, st["consensus"]["labels"], n_p, device)
+            st["consensus"].update({"match_inter": cm["inter"], "match_csize": cm["csize"],
+                                    "match_stability": cm["stability"], "match_recovered": cm["recovered"],
+                                    "match_dissolved": cm["dissolved"]})
     if gather and world > 1 and out_shared and out is not None:
         # every rank downloads its rows into the shared host array; the barrier orders the
         # writes before rank 0 hands the array back

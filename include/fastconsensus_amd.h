@@ -29,7 +29,9 @@
  *     reference labeling of fc_score_set_reference and the labelings.
  *     fc_community_quality and fc_community_graph depend on the chosen graph and their arguments
  *     alone and leave graph, labelings, reference, hierarchy and random state as they were;
- *     fc_cluster_coassoc reads the labelings as well and leaves the same.
+ *     fc_cluster_coassoc reads the labelings as well and leaves the same.  fc_cluster_match
+ *     depends on its arguments and, without `other`, on the labelings; it leaves labelings,
+ *     reference, hierarchy, working graph and random state as they were.
  */
 #ifndef FASTCONSENSUS_AMD_H
 #define FASTCONSENSUS_AMD_H
@@ -623,6 +625,46 @@ int fc_cluster_coassoc(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const
  * enabled: ms[3] = pairs (upload, segments of P, cluster ranks, sides, sort of the pairs), count
  * (the register-list kernel), fallback (the exact sort-based path). */
 int fc_cluster_coassoc_timing(fc_ctx* ctx, double* ms);
+
+/* ---- cluster-wise Jaccard best match of a given partition ------------------------------- */
+/* For a partition P of the nodes with clusters k of size s_k, and a labeling r with t_r(d) = the
+ * nodes (of all n) that r labels d and C_r[k][d] = the members of k that r labels d:
+ *   J_r(k, d)   = C / (s_k + t_r(d) - C),   C = C_r[k][d] > 0          the Jaccard index
+ *   best_r(k)   = the d of largest J_r(k, d); two fractions are compared exactly as C1 * U2 against
+ *                 C2 * U1 with U = s_k + t - C (C <= n < 2^31, U < 2^32: 64-bit products); among
+ *                 equal J the larger C (equal J and equal C force equal t)
+ *   inter[r][k] = C_r[k][best_r(k)]          csize[r][k] = t_r(best_r(k))
+ * Every cluster has a member, so a match exists, and the pair (inter, csize) is unique: it depends
+ * neither on how r numbers its communities nor on any floating-point value.  Hennig's cluster-wise
+ * stability of k is the mean over r of inter / (s_k + csize - inter); with P a planted partition
+ * and one found partition as r, inter / csize, inter / s_k and 2 inter / (s_k + csize) are the
+ * best-match precision, recall and F1 of each planted community.  Rows are independent: ranks
+ * gather theirs in replica order.  Read-only: the reuse paragraph at the top of this header. */
+typedef struct fc_match_info {
+    int64_t k, max_size, singletons;
+    int64_t perfect;        /* (r, k) with inter == s_k == csize, i.e. J = 1 */
+    int64_t inter_total;    /* sum of inter over all (r, k) */
+    int64_t slow_members;   /* (member, replica) pairs the exact fallback handled (diagnostic) */
+    int32_t n_r, pad;       /* rows written: the local replica count, or 1 with `other` */
+} fc_match_info;
+/* labels: host int32[n], P in node order, ids in [0, n), not necessarily dense; the K distinct ids
+ * are reported ascending.  other: NULL for the local labelings (n_r rows), or one host labeling
+ * int32[n] with ids in [0, n), matched as a single row: that form needs a loaded graph but no
+ * labelings and leaves the labelings untouched.  ids_out, size_out: host arrays of capacity n, the
+ * first K entries written.  dev_inter, dev_csize: device int32, row r at offset r * ld, the first K
+ * entries of each row written and the rest left alone.  ld < K with either buffer given is
+ * FC_EINVAL, and then only info->k is written (the caller sizes its buffers from it); with both
+ * buffers NULL ld is ignored and ids, sizes and info are reported.  Any output may be NULL.  All
+ * work on the context's stream; returns after it finished.  FC_ESTATE: no graph, or other == NULL
+ * with no labelings; FC_ELIMIT: more than 2048 local replicas; FC_EINVAL: labels NULL, or an id of
+ * labels or other outside [0, n) (the message names the array and the index; checked before any
+ * launch).  Apart from info->k in the ld case nothing is written on error. */
+int fc_cluster_match(fc_ctx* ctx, const int32_t* labels, const int32_t* other, int64_t ld,
+                     int32_t* ids_out, int64_t* size_out, void* dev_inter, void* dev_csize, fc_match_info* info);
+/* Device time (ms, HIP events) of the phases of the last fc_cluster_match made with timing
+ * enabled: ms[4] = segments (upload, sort, run lengths), sizes (the community-size table), match
+ * (the register-list kernel), fallback (the exact sort-based path). */
+int fc_cluster_match_timing(fc_ctx* ctx, double* ms);   /* ms[4] = segments, sizes, match, fallback */
 
 /* ---- synthetic inputs for benchmarks (host C++, not on the hot path) ---------------- */
 /* LFR-like benchmark graph (power-law degrees tau1, community sizes tau2, mixing mu).
