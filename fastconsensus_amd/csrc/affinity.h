@@ -4,21 +4,22 @@
 // (v itself counted when P(v) = k), for a list of (node, cluster) queries: the numerator of Monti's
 // item consensus m_i(k) for any k, and what a one-element move of the median-partition objective
 // needs.  Exact integers, sums over replicas (ranks add theirs), no matrix.
-// Included at the end of consensus.hip after vote.h (cluster.h's k_cc_row_slots, k_cc_emit and
-// cc_sum4, score.h's segments, fallback entries, SC_D and ScLabT, coassoc.h's k_ca_map and
-// analysis.h's PhaseMarks are in scope).
+// Included at the end of consensus.hip after vote.h (cluster.h's cell_chunks, score.h's segments,
+// cell-kernel pieces, fallback plan and ScLabT, coassoc.h's k_ca_map and analysis.h's PhaseMarks are
+// in scope).
 //
 // Queries: a query's cluster id becomes its rank among P's ascending ids (a binary search of
 // score_segments' unique labels; an id that does not occur gets rank k), the query indices are
 // sorted by rank, and the run lengths of the sorted ranks are the queried clusters with their query
 // segments.
-// Count: k_cc_count's walk, one wave per QUERIED cluster, LANES ARE REPLICAS.  Pass 1 builds the
+// Count: one wave per QUERIED cluster, LANES ARE REPLICAS.  Pass 1 (sc_list_walk) builds the
 // lane's (label, count) list of the cluster's members in SC_D registers; pass 2 walks the cluster's
-// queries instead of its members, looks each query node's label up in the list and adds the four
-// wave sums of cc_sum4 to out[query].  A cluster no query names is never touched.
+// queries instead of its members, looks each query node's label up in the list (sc_gather4,
+// sc_list_count) and adds the four wave sums of sc_sum4 to out[query].  A cluster no query names
+// is never touched.
 // Fallback: a lane with a ninth label, and every lane of a cluster past the length cap, is flagged
-// in ovf[bank * k + cluster] (cluster.h's entries); k_cc_emit's keys are sorted and run-length
-// encoded chunk by chunk, and one thread per (query, replica) whose lane is flagged binary-searches
+// in ovf[bank * k + cluster] (score.h's entries); cell_chunks sorts and run-length encodes their
+// keys chunk by chunk, and one thread per (query, replica) whose lane is flagged binary-searches
 // the chunk's unique keys for (slot, lab_r(v)).  A slot lies in exactly one chunk, so no cell is split.
 #pragma once
 #include <algorithm>
@@ -55,7 +56,7 @@ __global__ __launch_bounds__(256) void k_ia_rank(int64_t np, const int32_t* __re
 // ------------------------------------------------------------------ count kernel (lanes are replicas)
 // qc[i]: the rank of the i-th queried cluster (k: the queries of ids that do not occur, skipped);
 // its queries are qidx[qoff[i] .. qoff[i + 1]), query q asking for internal vertex qv[q].
-// lcap as in k_cc_count.  ovf[bank * k + cluster], zeroed by the caller: the lanes left to the
+// lcap: score_list_cap with sum32.  ovf[bank * k + cluster], zeroed by the caller: the lanes left to the
 // fallback.  out[query] zeroed by the caller.
 __global__ __launch_bounds__(256) void k_ia_count(int64_t nq, const uint32_t* __restrict__ qc,
                                                   const int32_t* __restrict__ qoff, const int32_t* __restrict__ qidx,
@@ -77,43 +78,8 @@ __global__ __launch_bounds__(256) void k_ia_count(int64_t nq, const uint32_t* __
         if (len <= lcap) {   // wave-uniform
             int32_t key[SC_D];
             int32_t cnt[SC_D];
-#pragma unroll
-            for (int d = 0; d < SC_D; ++d) { key[d] = -1; cnt[d] = 0; }
             // pass 1: the list of (label, count) of this lane's replica over the cluster's members
-            for (int32_t b0 = s0; b0 < s1; b0 += 64) {
-                if (!__any(act && !ov)) break;
-                const int nb = s1 - b0 < 64 ? s1 - b0 : 64;
-                const int32_t myv = b0 + lane < s1 ? sval[b0 + lane] : 0;
-                for (int t = 0; t < nb; t += 4) {
-                    int32_t l[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {   // four rows in flight before the list updates
-                        const int tt = t + j < nb ? t + j : nb - 1;
-                        const int32_t v = __shfl(myv, tt);
-                        l[j] = act ? col[(int64_t)v * ldT] : 0;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (t + j < nb && act && !ov) {
-                            const int32_t lab = l[j];
-                            bool f = false;
-#pragma unroll
-                            for (int d = 0; d < SC_D; ++d) {
-                                const bool h = key[d] == lab;
-                                cnt[d] += h ? 1 : 0;
-                                f |= h;
-                            }
-                            if (!f) {
-                                bool placed = false;
-#pragma unroll
-                                for (int d = 0; d < SC_D; ++d)
-                                    if (!placed && key[d] < 0) { key[d] = lab; cnt[d] = 1; placed = true; }
-                                if (!placed) ov = true;
-                            }
-                        }
-                    }
-                }
-            }
+            sc_list_walk(key, cnt, s0, s1, sval, col, ldT, act, ov, lane);
             const bool live = act && !ov;
             // pass 2: the cluster's queries against the lists still in registers
             if (__any(live)) {   // wave-uniform
@@ -124,21 +90,14 @@ __global__ __launch_bounds__(256) void k_ia_count(int64_t nq, const uint32_t* __
                     const int32_t myv = b0 + lane < q1 ? qv[myq] : 0;
                     for (int t = 0; t < nb; t += 4) {
                         int32_t l[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int tt = t + j < nb ? t + j : nb - 1;
-                            const int32_t v = __shfl(myv, tt);
-                            l[j] = live ? col[(int64_t)v * ldT] : 0;
-                        }
+                        sc_gather4(l, myv, t, nb, col, ldT, live);
                         unsigned n[4];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            int32_t x = 0;
-#pragma unroll
-                            for (int d = 0; d < SC_D; ++d) x += key[d] == l[j] ? cnt[d] : 0;
+                            const int32_t x = sc_list_count(key, cnt, l[j]);
                             n[j] = live && t + j < nb ? (unsigned)x : 0u;
                         }
-                        const unsigned tot = cc_sum4(n, lane);
+                        const unsigned tot = sc_sum4(n, lane);
                         const int tj = t + (lane >> 4);   // the query this lane's group of 16 summed
                         const int32_t q = __shfl(myq, tj < nb ? tj : nb - 1);
                         if ((lane & 15) == 0 && tj < nb && tot) atomicAdd(&out[q], (unsigned long long)tot);
@@ -163,7 +122,7 @@ __global__ __launch_bounds__(256) void k_ia_slow(int64_t np, int banks, const ui
         const int64_t cc = (int64_t)qrank[p];
         if (cc < k) s += (unsigned long long)__popcll(ovf[bank * k + cc]);
     }
-    s = cc_wave_sum(s);
+    s = sc_wave_sum(s);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(&ctr[IA_SLOW], s);
 }
 // One thread per (query p, replica r) of a flagged lane: the chunk's unique keys hold the cell
@@ -198,32 +157,14 @@ __global__ __launch_bounds__(256) void k_ia_lookup(int64_t np, int banks, int n_
 }
 static void affinity_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned long long* ovf, int64_t np,
                               const uint32_t* qrank, const int32_t* qv, unsigned long long* out) {
-    const int64_t N = c.N, nbk = (int64_t)banks * s.k;
-    int64_t* cnt = ensure<int64_t>(c.sc_e1, nbk + 1);
-    int64_t* E = ensure<int64_t>(c.sc_e2, nbk + 1);
-    k_sc_ovf_keys<<<nblk(nbk + 1), TB, 0, c.stream>>>(nbk, s.k, ovf, s.seg, cnt);
-    exclusive_scan(c, (const int64_t*)cnt, E, nbk + 1);
-    const int64_t T = read_i64(c, E + nbk);
-    if (T == 0) return;
-    FC_REQUIRE(nbk * 64 < ((int64_t)1 << 32), FC_ELIMIT, "too many (cluster, replica) slots for the item-affinity fallback");
-    const int64_t cap = std::max<int64_t>(2 * N, c.score_chunk), step = cap - N;
-    unsigned long long* k1 = (unsigned long long*)ensure<uint64_t>(c.sc_fk1, cap);
-    unsigned long long* k2 = (unsigned long long*)ensure<uint64_t>(c.sc_fk2, cap);
-    int32_t* v1 = ensure<int32_t>(c.cc_fv1, cap);   // k_cc_emit's member vertices: not needed here
-    int32_t* rc = ensure<int32_t>(c.sc_fcnt, cap + 1);
-    int32_t* nr = ensure<int32_t>(c.sc_nruns, 4);
+    const ScPlan p = score_fallback_plan(c, s, (int64_t)banks * s.k, ovf,
+                                         "too many (cluster, replica) slots for the item-affinity fallback");
+    if (p.T == 0) return;
     const int64_t threads = np * banks * 64;
-    for (int64_t lo = 0; lo < T; lo += step) {
-        const int64_t hi = lo + step, n = std::min<int64_t>(cap, T - lo);
-        FC_HIP(hipMemsetAsync(k1, 0xff, sizeof(uint64_t) * (size_t)n, c.stream));
-        k_cc_emit<<<std::min<unsigned>(nblk(n), 8192u), TB, 0, c.stream>>>(nbk, s.k, E, ovf, s.seg, s.sval,
-                                                                          c.labT.as<int32_t>(), c.ldT, lo, hi, n, k1, v1);
-        sort_keys_public(c, (const uint64_t*)k1, (uint64_t*)k2, n, 64);
-        run_length(c, (const unsigned long long*)k2, k1, rc, nr, n);
-        k_ia_lookup<<<std::min<unsigned>(nblk(threads), 8192u), TB, 0, c.stream>>>(np, banks, c.n_r, qrank, qv, s.k, ovf,
-                                                                                  c.labT.as<int32_t>(), c.ldT, nr, k1, rc,
-                                                                                  out);
-    }
+    cell_chunks<false>(c, s, p, ovf, c.labT.as<int32_t>(), c.ldT, [&](const CellChunk& ch) {
+        k_ia_lookup<<<std::min<unsigned>(nblk(threads), 8192u), TB, 0, c.stream>>>(
+            np, banks, c.n_r, qrank, qv, s.k, ovf, c.labT.as<int32_t>(), c.ldT, ch.nruns, ch.ukeys, ch.counts, out);
+    });
 }
 
 // labels: host int32[N] in node order; nodes, clusters: host int32[np]; all ids in [0, N),
@@ -231,17 +172,12 @@ static void affinity_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned 
 void item_affinity(Ctx& c, const int32_t* labels, int64_t np, const int32_t* nodes, const int32_t* clusters,
                    int64_t* dev_out, fc_affinity_info* info) {
     score_require(c);
-    const int64_t N = c.N;
     const int banks = (c.n_r + 63) / 64;
     PhaseMarks ph(c, c.ia_ms);
     ph.clear();
     ScLabT lt(c);
     ph.mark();
-    int32_t* in = ensure<int32_t>(c.st_lab, N + 1);
-    FC_HIP(hipMemcpyAsync(in, labels, 4 * (size_t)N, hipMemcpyHostToDevice, c.stream));
-    int32_t* row = ensure<int32_t>(c.cc_row, N);
-    k_cc_row_slots<<<nblk(N), TB, 0, c.stream>>>(N, in, c.tpos.as<int32_t>(), row);
-    const ScSeg s = score_segments(c, (const int32_t*)row);
+    const ScSeg s = partition_segments(c, partition_upload(c, labels));
     // the lists: nodes -> internal vertices, cluster ids -> ranks, query indices by rank
     int32_t* ids = ensure<int32_t>(c.ia_ids, (size_t)2 * np);
     FC_HIP(hipMemcpyAsync(ids, nodes, 4 * (size_t)np, hipMemcpyHostToDevice, c.stream));
@@ -270,10 +206,9 @@ void item_affinity(Ctx& c, const int32_t* labels, int64_t np, const int32_t* nod
     ph.mark();   // queries
     unsigned long long* ovf = (unsigned long long*)ensure<uint64_t>(c.sc_ovf, (size_t)banks * s.k + 1);
     FC_HIP(hipMemsetAsync(ovf, 0, sizeof(uint64_t) * ((size_t)banks * s.k + 1), c.stream));
-    const int lcap = c.score_slow ? 0 : std::min(c.score_lcap, 1 << 24);
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((nq + 3) / 4, SC_GRID));
-    k_ia_count<<<dim3(gx, banks), TB, 0, c.stream>>>(nq, qc, qoff, idx + np, qv, s.k, s.seg, s.sval, c.labT.as<int32_t>(),
-                                                     c.ldT, c.n_r, lcap, ovf, out);
+    k_ia_count<<<dim3(score_count_grid(nq), banks), TB, 0, c.stream>>>(nq, qc, qoff, idx + np, qv, s.k, s.seg, s.sval,
+                                                                      c.labT.as<int32_t>(), c.ldT, c.n_r,
+                                                                      score_list_cap(c, true), ovf, out);
     ph.mark();   // count
     k_ia_slow<<<std::min<unsigned>(nblk(np * banks), 1024u), TB, 0, c.stream>>>(np, banks, key, s.k, ovf, ctr);
     affinity_fallback(c, s, banks, ovf, np, key, qv, out);

@@ -5,68 +5,43 @@
 // labels d,
 //     pairs[k] = sum_r sum_d C_r[k][d]^2        item[v] = sum_r C_r[P(v)][lab_r(v)]
 // exact integers, sums over replicas (ranks add theirs), O(N n_r) work.
-// Included at the end of consensus.hip after coassoc.h (score.h's segments, fallback entries and
-// ScLabT, analysis.h's PhaseMarks and the hipcub wrappers are in scope).
+// Included at the end of consensus.hip after coassoc.h (score.h's segments, cell-kernel pieces,
+// fallback plan and ScLabT, analysis.h's PhaseMarks and the hipcub wrappers are in scope).
 //
-// The count kernel is k_sc_pairs' walk with the per-cluster structure kept: one wave per cluster
-// of P, LANES ARE REPLICAS, each lane building the (label, count) list of its replica in SC_D
-// registers.  At the segment's end the lists are the rows C_r[k][.]: the wave adds their squares
-// to pairs[k], then streams the members a second time and adds each lane's count of its own label
-// for that member to item[v].  A lane with a ninth label, and every lane of a cluster longer than
-// the length cap, is left to the exact fallback: score.h's entries and chunks, each key carrying
-// its member's vertex through the sort.  Every contribution is an int64 atomicAdd of an integer, so
-// neither the order nor the split over banks and paths shows in the result.
+// The count kernel keeps the per-cluster structure: one wave per cluster of P, LANES ARE REPLICAS,
+// each lane building the (label, count) list of its replica in SC_D registers (sc_list_walk).  At
+// the segment's end the lists are the rows C_r[k][.]: the wave adds their squares to pairs[k], then
+// streams the members a second time and adds each lane's count of its own label for that member
+// (sc_gather4, sc_list_count) to item[v].  A lane with a ninth label, and every lane of a cluster
+// longer than the length cap, is left to the exact fallback: score.h's entries, here emitted one
+// thread per key and sorted, run-length encoded and handed to the caller's kernel chunk by chunk
+// (cell_chunks, which vote.h, affinity.h, merge.h and match.h run as well), each key of this call
+// carrying its member's vertex through the sort.  Every contribution is an int64 atomicAdd of an
+// integer, so neither the order nor the split over banks and paths shows in the result.
 #pragma once
 #include <algorithm>
 #include <vector>
 
 namespace fc {
 
-// row[tpos[t]] = in[t]: the caller's partition (node order) as a label row in slot order
-__global__ void k_cc_row_slots(int64_t N, const int32_t* __restrict__ in, const int32_t* __restrict__ tpos,
-                               int32_t* __restrict__ row) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < N) row[tpos[t]] = in[t];
-}
 // out[t] = item[sigma[t]]: sums by internal vertex -> node order
 __global__ void k_cc_item_out(int64_t N, const unsigned long long* __restrict__ item, const int32_t* __restrict__ sigma,
                               int64_t* __restrict__ out) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < N) out[t] = (int64_t)item[sigma[t]];
 }
-__device__ __forceinline__ unsigned long long cc_wave_sum(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
 // *total += sum of x[0 .. n)
 __global__ __launch_bounds__(256) void k_cc_total(int64_t n, const unsigned long long* __restrict__ x,
                                                   unsigned long long* __restrict__ total) {
     unsigned long long s = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) s += x[i];
-    s = cc_wave_sum(s);
+    s = sc_wave_sum(s);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(total, s);
 }
 
-// Four per-lane values -> their four wave sums in 7 shuffles: the halves of the wave trade two
-// values, the quarters one, and four steps finish inside each group of 16 lanes.  The lanes with
-// (lane & 15) == 0 return the sum of value lane >> 4; the others return partial sums.
-__device__ __forceinline__ unsigned cc_sum4(const unsigned (&c)[4], int lane) {
-    const bool hi = lane & 32, h2 = lane & 16;
-    unsigned a0 = hi ? c[2] : c[0], a1 = hi ? c[3] : c[1];
-    a0 += __shfl_xor(hi ? c[0] : c[2], 32);
-    a1 += __shfl_xor(hi ? c[1] : c[3], 32);
-    unsigned b = h2 ? a1 : a0;
-    b += __shfl_xor(h2 ? a0 : a1, 16);
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) b += __shfl_xor(b, o);
-    return b;
-}
-
 // ------------------------------------------------------------------ count kernel (lanes are replicas)
-// lcap: longest cluster one wave streams (0: everything to the fallback; at most 2^24, so that a
-// member's wave sum fits 32 bits).  ovf[bank * k + cluster]: the lanes left to the fallback.
-// pairs[cluster] and item[internal vertex] are zeroed by the caller.
+// lcap: longest cluster one wave streams (score_list_cap with sum32).  ovf[bank * k + cluster]: the
+// lanes left to the fallback.  pairs[cluster] and item[internal vertex] are zeroed by the caller.
 __global__ __launch_bounds__(256) void k_cc_count(int64_t k, const int32_t* __restrict__ seg,
                                                   const int32_t* __restrict__ sval,
                                                   const int32_t* __restrict__ labT, int ldT, int n_r, int lcap,
@@ -84,50 +59,15 @@ __global__ __launch_bounds__(256) void k_cc_count(int64_t k, const int32_t* __re
         if (len <= lcap) {   // wave-uniform
             int32_t key[SC_D];
             int32_t cnt[SC_D];
-#pragma unroll
-            for (int d = 0; d < SC_D; ++d) { key[d] = -1; cnt[d] = 0; }
             // pass 1: the list of (label, count) of this lane's replica over the cluster's members
-            for (int32_t b0 = s0; b0 < s1; b0 += 64) {
-                if (!__any(act && !ov)) break;
-                const int nb = s1 - b0 < 64 ? s1 - b0 : 64;
-                const int32_t myv = b0 + lane < s1 ? sval[b0 + lane] : 0;
-                for (int t = 0; t < nb; t += 4) {
-                    int32_t l[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {   // four rows in flight before the list updates
-                        const int tt = t + j < nb ? t + j : nb - 1;
-                        const int32_t v = __shfl(myv, tt);
-                        l[j] = act ? col[(int64_t)v * ldT] : 0;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (t + j < nb && act && !ov) {
-                            const int32_t lab = l[j];
-                            bool f = false;
-#pragma unroll
-                            for (int d = 0; d < SC_D; ++d) {
-                                const bool h = key[d] == lab;
-                                cnt[d] += h ? 1 : 0;
-                                f |= h;
-                            }
-                            if (!f) {
-                                bool placed = false;
-#pragma unroll
-                                for (int d = 0; d < SC_D; ++d)
-                                    if (!placed && key[d] < 0) { key[d] = lab; cnt[d] = 1; placed = true; }
-                                if (!placed) ov = true;
-                            }
-                        }
-                    }
-                }
-            }
+            sc_list_walk(key, cnt, s0, s1, sval, col, ldT, act, ov, lane);
             const bool live = act && !ov;
             unsigned long long sq = 0;
             if (live) {
 #pragma unroll
                 for (int d = 0; d < SC_D; ++d) sq += (unsigned long long)cnt[d] * (unsigned long long)cnt[d];
             }
-            sq = cc_wave_sum(sq);
+            sq = sc_wave_sum(sq);
             if (lane == 0 && sq) atomicAdd(&pairs[cc], sq);
             // pass 2: the same members against the lists still in registers
             if (sq) {   // wave-uniform: some lane is live
@@ -136,21 +76,14 @@ __global__ __launch_bounds__(256) void k_cc_count(int64_t k, const int32_t* __re
                     const int32_t myv = b0 + lane < s1 ? sval[b0 + lane] : 0;
                     for (int t = 0; t < nb; t += 4) {
                         int32_t l[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int tt = t + j < nb ? t + j : nb - 1;
-                            const int32_t v = __shfl(myv, tt);
-                            l[j] = live ? col[(int64_t)v * ldT] : 0;
-                        }
+                        sc_gather4(l, myv, t, nb, col, ldT, live);
                         unsigned n[4];
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            int32_t x = 0;
-#pragma unroll
-                            for (int d = 0; d < SC_D; ++d) x += key[d] == l[j] ? cnt[d] : 0;
+                            const int32_t x = sc_list_count(key, cnt, l[j]);
                             n[j] = live && t + j < nb ? (unsigned)x : 0u;
                         }
-                        const unsigned tot = cc_sum4(n, lane);
+                        const unsigned tot = sc_sum4(n, lane);
                         const int tj = t + (lane >> 4);   // the member this lane's group of 16 summed
                         const int32_t v = __shfl(myv, tj < nb ? tj : nb - 1);
                         if ((lane & 15) == 0 && tj < nb && tot) atomicAdd(&item[v], (unsigned long long)tot);
@@ -164,7 +97,7 @@ __global__ __launch_bounds__(256) void k_cc_count(int64_t k, const int32_t* __re
 }
 
 // ------------------------------------------------------------------ exact fallback, with member identity
-// score.h's entries, prefix sums E and chunk windows (k_sc_ovf_keys); a key
+// score.h's entries, prefix sums E and chunk windows (score_fallback_plan); a key
 // (entry * 64 + lane) << 32 | label now travels with its member's vertex as the sort value.
 // One thread per key position p of the chunk [lo, lo + n): the key lo + p lies in entry i
 // (E[i] <= lo + p < E[i + 1]), item q of it (its q-th set lane) and is member t of the cluster.  The
@@ -226,38 +159,54 @@ __global__ __launch_bounds__(256) void k_cc_fold(int64_t n, const int32_t* __res
         if ((int64_t)S[a] == j) atomicAdd(&pairs[(int64_t)(((key >> 32) >> 6) % (unsigned long long)k)], c * c);
     }
 }
+namespace {
+// one chunk of the fallback, sorted and run-length encoded: the n keys of the chunk make *nruns runs,
+// run j = one contingency cell (ukeys[j], its counts[j] members), the padding's run last.  With the
+// members kept: svals[p] = the vertex of sorted key p, S = the exclusive prefix sums of counts.
+struct CellChunk {
+    int64_t n;
+    const unsigned long long* ukeys;
+    const int32_t *counts, *nruns, *svals, *S;
+};
+}  // namespace
+// The chunk loop of every cell call's fallback after score_fallback_plan: k_cc_emit's keys of the
+// replica columns labT / ldT, the sort and the run lengths, then fold(chunk) launches the call's own
+// fold or lookup kernel on the stream.  MEMBERS: each key takes its member's vertex through the
+// sort and the run lengths are scanned (cluster consensus alone adds per member).
+template <bool MEMBERS, class Fold>
+static void cell_chunks(Ctx& c, const ScSeg& s, const ScPlan& p, const unsigned long long* ovf, const int32_t* labT, int ldT,
+                        Fold fold) {
+    const ScChunkBufs b = score_chunk_buffers(c);
+    int32_t* v1 = ensure<int32_t>(c.cc_fv1, b.cap);   // k_cc_emit writes them either way
+    int32_t* v2 = MEMBERS ? ensure<int32_t>(c.cc_fv2, b.cap) : nullptr;
+    int32_t* S = MEMBERS ? ensure<int32_t>(c.cc_fscan, b.cap + 1) : nullptr;
+    for (int64_t lo = 0; lo < p.T; lo += b.step) {
+        const int64_t hi = lo + b.step, n = std::min<int64_t>(b.cap, p.T - lo);
+        FC_HIP(hipMemsetAsync(b.k1, 0xff, sizeof(uint64_t) * (size_t)n, c.stream));
+        if (MEMBERS) {
+            FC_HIP(hipMemsetAsync(v1, 0, sizeof(int32_t) * (size_t)n, c.stream));
+            FC_HIP(hipMemsetAsync(b.rc, 0, sizeof(int32_t) * (size_t)(n + 1), c.stream));   // run lengths past the last run: 0
+        }
+        k_cc_emit<<<std::min<unsigned>(nblk(n), 8192u), TB, 0, c.stream>>>(p.nbk, s.k, p.E, ovf, s.seg, s.sval, labT, ldT, lo,
+                                                                          hi, n, b.k1, v1);
+        if (MEMBERS) sort_pairs_public(c, (const uint64_t*)b.k1, (uint64_t*)b.k2, (const int32_t*)v1, v2, n, 64);
+        else sort_keys_public(c, (const uint64_t*)b.k1, (uint64_t*)b.k2, n, 64);
+        run_length(c, (const unsigned long long*)b.k2, b.k1, b.rc, b.nr, n);
+        if (MEMBERS) exclusive_scan(c, (const int32_t*)b.rc, S, n + 1);
+        fold(CellChunk{n, b.k1, b.rc, b.nr, v2, S});
+    }
+}
 // returns the (member, replica) pairs handled here
 static int64_t cluster_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned long long* ovf,
                                 unsigned long long* pairs, unsigned long long* item) {
-    const int64_t N = c.N, nbk = (int64_t)banks * s.k;
-    int64_t* cnt = ensure<int64_t>(c.sc_e1, nbk + 1);
-    int64_t* E = ensure<int64_t>(c.sc_e2, nbk + 1);
-    k_sc_ovf_keys<<<nblk(nbk + 1), TB, 0, c.stream>>>(nbk, s.k, ovf, s.seg, cnt);
-    exclusive_scan(c, (const int64_t*)cnt, E, nbk + 1);
-    const int64_t T = read_i64(c, E + nbk);
-    if (T == 0) return 0;
-    FC_REQUIRE(nbk * 64 < ((int64_t)1 << 32), FC_ELIMIT, "too many (cluster, replica) slots for the cluster-consensus fallback");
-    const int64_t cap = std::max<int64_t>(2 * N, c.score_chunk), step = cap - N;
-    unsigned long long* k1 = (unsigned long long*)ensure<uint64_t>(c.sc_fk1, cap);
-    unsigned long long* k2 = (unsigned long long*)ensure<uint64_t>(c.sc_fk2, cap);
-    int32_t* v1 = ensure<int32_t>(c.cc_fv1, cap);
-    int32_t* v2 = ensure<int32_t>(c.cc_fv2, cap);
-    int32_t* rc = ensure<int32_t>(c.sc_fcnt, cap + 1);
-    int32_t* S = ensure<int32_t>(c.cc_fscan, cap + 1);
-    int32_t* nr = ensure<int32_t>(c.sc_nruns, 4);
-    for (int64_t lo = 0; lo < T; lo += step) {
-        const int64_t hi = lo + step, n = std::min<int64_t>(cap, T - lo);
-        FC_HIP(hipMemsetAsync(k1, 0xff, sizeof(uint64_t) * (size_t)n, c.stream));
-        FC_HIP(hipMemsetAsync(v1, 0, sizeof(int32_t) * (size_t)n, c.stream));
-        FC_HIP(hipMemsetAsync(rc, 0, sizeof(int32_t) * (size_t)(n + 1), c.stream));   // run lengths past the last run: 0
-        k_cc_emit<<<std::min<unsigned>(nblk(n), 8192u), TB, 0, c.stream>>>(nbk, s.k, E, ovf, s.seg, s.sval,
-                                                                          c.labT.as<int32_t>(), c.ldT, lo, hi, n, k1, v1);
-        sort_pairs_public(c, (const uint64_t*)k1, (uint64_t*)k2, (const int32_t*)v1, v2, n, 64);
-        run_length(c, (const unsigned long long*)k2, k1, rc, nr, n);
-        exclusive_scan(c, (const int32_t*)rc, S, n + 1);
-        k_cc_fold<<<std::min<unsigned>(nblk(n), 4096u), TB, 0, c.stream>>>(n, nr, k1, rc, S, v2, s.k, pairs, item);
-    }
-    return T;
+    const ScPlan p = score_fallback_plan(c, s, (int64_t)banks * s.k, ovf,
+                                         "too many (cluster, replica) slots for the cluster-consensus fallback");
+    if (p.T == 0) return 0;
+    cell_chunks<true>(c, s, p, ovf, c.labT.as<int32_t>(), c.ldT, [&](const CellChunk& ch) {
+        k_cc_fold<<<std::min<unsigned>(nblk(ch.n), 4096u), TB, 0, c.stream>>>(ch.n, ch.nruns, ch.ukeys, ch.counts, ch.S,
+                                                                             ch.svals, s.k, pairs, item);
+    });
+    return p.T;
 }
 
 // labels: host int32[N] in node order, ids in [0, N), validated by the caller.  Synchronises.
@@ -270,11 +219,7 @@ void cluster_consensus(Ctx& c, const int32_t* labels, int32_t* ids_out, int64_t*
     ph.clear();
     ScLabT lt(c);
     ph.mark();
-    int32_t* in = ensure<int32_t>(c.st_lab, N + 1);
-    FC_HIP(hipMemcpyAsync(in, labels, 4 * (size_t)N, hipMemcpyHostToDevice, c.stream));
-    int32_t* row = ensure<int32_t>(c.cc_row, N);
-    k_cc_row_slots<<<nblk(N), TB, 0, c.stream>>>(N, in, c.tpos.as<int32_t>(), row);
-    const ScSeg s = score_segments(c, (const int32_t*)row);
+    const ScSeg s = partition_segments(c, partition_upload(c, labels));
     ph.mark();   // segments
     unsigned long long* pairs = (unsigned long long*)ensure<uint64_t>(c.cc_pairs, N);
     unsigned long long* item = (unsigned long long*)ensure<uint64_t>(c.cc_item, N);
@@ -283,32 +228,23 @@ void cluster_consensus(Ctx& c, const int32_t* labels, int32_t* ids_out, int64_t*
     FC_HIP(hipMemsetAsync(pairs, 0, sizeof(uint64_t) * (size_t)N, c.stream));
     FC_HIP(hipMemsetAsync(item, 0, sizeof(uint64_t) * (size_t)N, c.stream));
     FC_HIP(hipMemsetAsync(tot, 0, sizeof(uint64_t), c.stream));
-    const int lcap = c.score_slow ? 0 : std::min(c.score_lcap, 1 << 24);
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((s.k + 3) / 4, SC_GRID));
-    k_cc_count<<<dim3(gx, banks), TB, 0, c.stream>>>(s.k, s.seg, s.sval, c.labT.as<int32_t>(), c.ldT, c.n_r, lcap, ovf,
-                                                     pairs, item);
+    k_cc_count<<<dim3(score_count_grid(s.k), banks), TB, 0, c.stream>>>(s.k, s.seg, s.sval, c.labT.as<int32_t>(), c.ldT, c.n_r,
+                                                                       score_list_cap(c, true), ovf, pairs, item);
     ph.mark();   // count
     const int64_t slow = cluster_fallback(c, s, banks, ovf, pairs, item);
     ph.mark();   // fallback
     k_cc_total<<<std::min<unsigned>(nblk(s.k), 1024u), TB, 0, c.stream>>>(s.k, pairs, tot);
-    std::vector<int32_t> hcnt((size_t)s.k), hid((size_t)s.k);
-    FC_HIP(hipMemcpyAsync(hcnt.data(), c.sc_cnt.as<int32_t>(), 4 * (size_t)s.k, hipMemcpyDeviceToHost, c.stream));
-    FC_HIP(hipMemcpyAsync(hid.data(), c.sc_ulab.as<int32_t>(), 4 * (size_t)s.k, hipMemcpyDeviceToHost, c.stream));
+    PartSummary sum;
+    sum.fetch(c, s.k);
     const int64_t total = read_i64(c, (const int64_t*)tot);   // synchronises
     ph.collect();
     if (dev_cluster) FC_HIP(hipMemcpyAsync(dev_cluster, pairs, sizeof(int64_t) * (size_t)N, hipMemcpyDeviceToDevice, c.stream));
     if (dev_item) k_cc_item_out<<<nblk(N), TB, 0, c.stream>>>(N, item, c.sigma.as<int32_t>(), dev_item);
     sync(c);
-    int64_t mx = 0, single = 0;
-    for (int64_t i = 0; i < s.k; ++i) {
-        mx = std::max<int64_t>(mx, hcnt[i]);
-        single += hcnt[i] == 1;
-        if (ids_out) ids_out[i] = hid[i];
-        if (size_out) size_out[i] = hcnt[i];
-    }
+    sum.finish(ids_out, size_out);
     if (info) {
         *info = fc_cluster_info{};
-        info->k = s.k; info->max_size = mx; info->singletons = single;
+        info->k = s.k; info->max_size = sum.max_size; info->singletons = sum.singletons;
         info->pairs_total = total; info->slow_members = slow; info->n_r = c.n_r;
     }
 }

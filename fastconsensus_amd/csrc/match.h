@@ -5,8 +5,8 @@
 //     s_k = the size of k, t_r(d) = the nodes (of all N) that r labels d,
 // reported as the two integers inter = C and csize = t of that community.  Hennig's cluster-wise
 // stability, recovered / dissolved counts and best-match F1 are functions of them (core.py).
-// Included at the end of consensus.hip after merge.h (score.h's segments, entries, chunks and
-// ScLabT, cluster.h's k_cc_row_slots, k_cc_emit and cc_wave_sum, analysis.h's PhaseMarks are in scope).
+// Included at the end of consensus.hip after merge.h (score.h's segments, cell-kernel pieces,
+// fallback plan and ScLabT, cluster.h's cell_chunks, analysis.h's PhaseMarks are in scope).
 //
 // The choice is made on integers alone: two fractions C1 / U1 and C2 / U2 (U = s + t - C) are
 // compared as C1 * U2 against C2 * U1 (C <= N < 2^31 and U < 2^32: the products fit 64 bits), and
@@ -15,15 +15,15 @@
 // place that compares; the register path, the fallback and the fallback's combine all call it.
 //
 // The sizes t_r(d) are one table per call in labT's layout, csz[d * ldT + r], so that a wave whose
-// lanes are replicas gathers them as it gathers labels.  The match kernel is k_cc_count's first
-// pass: one wave per cluster, LANES ARE REPLICAS, each lane building the (label, count) list of its
-// replica in SC_D registers; at the segment's end the lane looks up t for its labels, keeps the best
-// pair and writes its own entry of the two tables (one writer per entry, no atomics).  A lane with a
-// ninth label, and every lane of a cluster longer than the length cap, goes to the exact fallback:
-// score.h's entries and chunks, sorted and run-length folded; a run is one cell (its length is C, its
-// label gives t) and is folded into its group's 64-bit slot (C << 32 | t) by a compare-and-swap loop
-// on cm_better.  The order is a total one on the pairs, so the slot ends at the same maximum however
-// the runs arrive and however the chunks cut the key stream.
+// lanes are replicas gathers them as it gathers labels.  The match kernel is score.h's
+// sc_list_walk: one wave per cluster, LANES ARE REPLICAS, each lane building the (label, count) list
+// of its replica in SC_D registers; at the segment's end the lane looks up t for its labels, keeps
+// the best pair and writes its own entry of the two tables (one writer per entry, no atomics).  A
+// lane with a ninth label, and every lane of a cluster longer than the length cap, goes to the exact
+// fallback: score.h's entries in cluster.h's cell_chunks, sorted and run-length folded; a run is one
+// cell (its length is C, its label gives t) and is folded into its group's 64-bit slot
+// (C << 32 | t) by a compare-and-swap loop on cm_better.  The order is a total one on the pairs, so
+// the slot ends at the same maximum however the runs arrive and however the chunks cut the key stream.
 #pragma once
 #include <algorithm>
 #include <optional>
@@ -77,42 +77,7 @@ __global__ __launch_bounds__(256) void k_cm_match(int64_t k, const int32_t* __re
         if (len <= lcap) {   // wave-uniform
             int32_t key[SC_D];
             int32_t cnt[SC_D];
-#pragma unroll
-            for (int d = 0; d < SC_D; ++d) { key[d] = -1; cnt[d] = 0; }
-            for (int32_t b0 = s0; b0 < s1; b0 += 64) {
-                if (!__any(act && !ov)) break;
-                const int nb = s1 - b0 < 64 ? s1 - b0 : 64;
-                const int32_t myv = b0 + lane < s1 ? sval[b0 + lane] : 0;
-                for (int t = 0; t < nb; t += 4) {
-                    int32_t l[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {   // four rows in flight before the list updates
-                        const int tt = t + j < nb ? t + j : nb - 1;
-                        const int32_t v = __shfl(myv, tt);
-                        l[j] = act ? col[(int64_t)v * ldT] : 0;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (t + j < nb && act && !ov) {
-                            const int32_t lab = l[j];
-                            bool f = false;
-#pragma unroll
-                            for (int d = 0; d < SC_D; ++d) {
-                                const bool h = key[d] == lab;
-                                cnt[d] += h ? 1 : 0;
-                                f |= h;
-                            }
-                            if (!f) {
-                                bool placed = false;
-#pragma unroll
-                                for (int d = 0; d < SC_D; ++d)
-                                    if (!placed && key[d] < 0) { key[d] = lab; cnt[d] = 1; placed = true; }
-                                if (!placed) ov = true;
-                            }
-                        }
-                    }
-                }
-            }
+            sc_list_walk(key, cnt, s0, s1, sval, col, ldT, act, ov, lane);
             if (act && !ov) {
                 uint32_t t[SC_D];
 #pragma unroll
@@ -190,8 +155,8 @@ __global__ __launch_bounds__(256) void k_cm_total(int64_t rows, int64_t k, const
         perfect += c == s && csize[r * ldc + cc] == s;
         sum += (unsigned long long)c;
     }
-    perfect = cc_wave_sum(perfect);
-    sum = cc_wave_sum(sum);
+    perfect = sc_wave_sum(perfect);
+    sum = sc_wave_sum(sum);
     if ((threadIdx.x & 63) == 0 && sum) {
         if (perfect) atomicAdd(&tot[0], perfect);
         atomicAdd(&tot[1], sum);
@@ -212,34 +177,18 @@ struct CmTables {
 
 // returns the (member, replica) pairs handled here
 static int64_t match_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned long long* ovf, const CmTables& m) {
-    const int64_t N = c.N, nbk = (int64_t)banks * s.k;
-    int64_t* cnt = ensure<int64_t>(c.sc_e1, nbk + 1);
-    int64_t* E = ensure<int64_t>(c.sc_e2, nbk + 1);
-    k_sc_ovf_keys<<<nblk(nbk + 1), TB, 0, c.stream>>>(nbk, s.k, ovf, s.seg, cnt);
-    exclusive_scan(c, (const int64_t*)cnt, E, nbk + 1);
-    const int64_t T = read_i64(c, E + nbk);
-    if (T == 0) return 0;
-    FC_REQUIRE(nbk * 64 < ((int64_t)1 << 32), FC_ELIMIT, "too many (cluster, replica) slots for the cluster-match fallback");
-    const int64_t cap = std::max<int64_t>(2 * N, c.score_chunk), step = cap - N;
-    unsigned long long* k1 = (unsigned long long*)ensure<uint64_t>(c.sc_fk1, cap);
-    unsigned long long* k2 = (unsigned long long*)ensure<uint64_t>(c.sc_fk2, cap);
-    int32_t* v1 = ensure<int32_t>(c.cc_fv1, cap);   // k_cc_emit's member vertices: not needed here
-    int32_t* rc = ensure<int32_t>(c.sc_fcnt, cap);
-    int32_t* nr = ensure<int32_t>(c.sc_nruns, 4);
-    unsigned long long* best = (unsigned long long*)ensure<uint64_t>(c.cm_best, (size_t)nbk * 64);
-    FC_HIP(hipMemsetAsync(best, 0, sizeof(uint64_t) * (size_t)nbk * 64, c.stream));
-    for (int64_t lo = 0; lo < T; lo += step) {
-        const int64_t hi = lo + step, n = std::min<int64_t>(cap, T - lo);
-        FC_HIP(hipMemsetAsync(k1, 0xff, sizeof(uint64_t) * (size_t)n, c.stream));
-        k_cc_emit<<<std::min<unsigned>(nblk(n), 8192u), TB, 0, c.stream>>>(nbk, s.k, E, ovf, s.seg, s.sval, m.labT, m.ldT,
-                                                                          lo, hi, n, k1, v1);
-        sort_keys_public(c, (const uint64_t*)k1, (uint64_t*)k2, n, 64);
-        run_length(c, (const unsigned long long*)k2, k1, rc, nr, n);
-        k_cm_fold<<<std::min<unsigned>(nblk(n), 4096u), TB, 0, c.stream>>>(nr, k1, rc, s.k, s.seg, m.csz, m.ldT, best);
-    }
-    k_cm_scatter<<<std::min<unsigned>(nblk(nbk * 64), 4096u), TB, 0, c.stream>>>(nbk, s.k, ovf, best, m.inter, m.ldi,
-                                                                                m.csize, m.ldc);
-    return T;
+    const ScPlan p = score_fallback_plan(c, s, (int64_t)banks * s.k, ovf,
+                                         "too many (cluster, replica) slots for the cluster-match fallback");
+    if (p.T == 0) return 0;
+    unsigned long long* best = (unsigned long long*)ensure<uint64_t>(c.cm_best, (size_t)p.nbk * 64);
+    FC_HIP(hipMemsetAsync(best, 0, sizeof(uint64_t) * (size_t)p.nbk * 64, c.stream));
+    cell_chunks<false>(c, s, p, ovf, m.labT, m.ldT, [&](const CellChunk& ch) {
+        k_cm_fold<<<std::min<unsigned>(nblk(ch.n), 4096u), TB, 0, c.stream>>>(ch.nruns, ch.ukeys, ch.counts, s.k, s.seg, m.csz,
+                                                                             m.ldT, best);
+    });
+    k_cm_scatter<<<std::min<unsigned>(nblk(p.nbk * 64), 4096u), TB, 0, c.stream>>>(p.nbk, s.k, ovf, best, m.inter, m.ldi,
+                                                                                  m.csize, m.ldc);
+    return p.T;
 }
 
 // labels, other: host int32[N] in node order, ids in [0, N), validated by the caller; other null:
@@ -252,11 +201,7 @@ void cluster_match(Ctx& c, const int32_t* labels, const int32_t* other, int64_t 
     std::optional<ScLabT> lt;   // the labelings' labT; with `other` the labelings are not looked at
     if (!other) lt.emplace(c);
     ph.mark();
-    int32_t* in = ensure<int32_t>(c.st_lab, N + 1);
-    FC_HIP(hipMemcpyAsync(in, labels, 4 * (size_t)N, hipMemcpyHostToDevice, c.stream));
-    int32_t* row = ensure<int32_t>(c.cc_row, N);
-    k_cc_row_slots<<<nblk(N), TB, 0, c.stream>>>(N, in, c.tpos.as<int32_t>(), row);
-    const ScSeg s = score_segments(c, (const int32_t*)row);   // synchronises: st_lab is free again
+    const ScSeg s = partition_segments(c, partition_upload(c, labels));   // synchronises: st_lab is free again
     ph.mark();   // segments
     if ((dev_inter || dev_csize) && ld < s.k) {
         if (info) info->k = s.k;
@@ -265,7 +210,7 @@ void cluster_match(Ctx& c, const int32_t* labels, const int32_t* other, int64_t 
     }
     CmTables m{};
     if (other) {
-        FC_HIP(hipMemcpyAsync(in, other, 4 * (size_t)N, hipMemcpyHostToDevice, c.stream));
+        const int32_t* in = partition_upload(c, other);
         int32_t* col = ensure<int32_t>(c.cm_col, N);
         k_cm_column<<<nblk(N), TB, 0, c.stream>>>(N, in, c.sigma.as<int32_t>(), col);
         m.labT = col; m.ldT = 1; m.n_r = 1;
@@ -285,32 +230,24 @@ void cluster_match(Ctx& c, const int32_t* labels, const int32_t* other, int64_t 
     unsigned long long* tot = (unsigned long long*)ensure<uint64_t>(c.cm_tot, 2);
     unsigned long long* ovf = (unsigned long long*)ensure<uint64_t>(c.sc_ovf, (size_t)banks * s.k + 1);
     FC_HIP(hipMemsetAsync(tot, 0, 2 * sizeof(uint64_t), c.stream));
-    const int lcap = c.score_slow ? 0 : c.score_lcap;
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((s.k + 3) / 4, SC_GRID));
-    k_cm_match<<<dim3(gx, banks), TB, 0, c.stream>>>(s.k, s.seg, s.sval, m.labT, m.ldT, m.n_r, lcap, m.csz, ovf, m.inter,
-                                                     m.ldi, m.csize, m.ldc);
+    k_cm_match<<<dim3(score_count_grid(s.k), banks), TB, 0, c.stream>>>(s.k, s.seg, s.sval, m.labT, m.ldT, m.n_r,
+                                                                       score_list_cap(c, false), m.csz, ovf, m.inter,
+                                                                       m.ldi, m.csize, m.ldc);
     ph.mark();   // match
     const int64_t slow = match_fallback(c, s, banks, ovf, m);
     ph.mark();   // fallback
     k_cm_total<<<std::min<unsigned>(nblk((int64_t)rows * s.k), 2048u), TB, 0, c.stream>>>(rows, s.k, s.seg, m.inter, m.ldi,
                                                                                          m.csize, m.ldc, tot);
-    std::vector<int32_t> hcnt((size_t)s.k), hid((size_t)s.k);
+    PartSummary sum;
     unsigned long long htot[2];
-    FC_HIP(hipMemcpyAsync(hcnt.data(), c.sc_cnt.as<int32_t>(), 4 * (size_t)s.k, hipMemcpyDeviceToHost, c.stream));
-    FC_HIP(hipMemcpyAsync(hid.data(), c.sc_ulab.as<int32_t>(), 4 * (size_t)s.k, hipMemcpyDeviceToHost, c.stream));
+    sum.fetch(c, s.k);
     FC_HIP(hipMemcpyAsync(htot, tot, sizeof(htot), hipMemcpyDeviceToHost, c.stream));
     sync(c);
     ph.collect();
-    int64_t mx = 0, single = 0;
-    for (int64_t i = 0; i < s.k; ++i) {
-        mx = std::max<int64_t>(mx, hcnt[i]);
-        single += hcnt[i] == 1;
-        if (ids_out) ids_out[i] = hid[i];
-        if (size_out) size_out[i] = hcnt[i];
-    }
+    sum.finish(ids_out, size_out);
     if (info) {
         *info = fc_match_info{};
-        info->k = s.k; info->max_size = mx; info->singletons = single;
+        info->k = s.k; info->max_size = sum.max_size; info->singletons = sum.singletons;
         info->perfect = (int64_t)htot[0]; info->inter_total = (int64_t)htot[1];
         info->slow_members = slow; info->n_r = rows;
     }

@@ -6,9 +6,9 @@
 // so that joining a and b changes the median-partition objective F by 2 (2 X(a, b) - R s_a s_b).
 // Exact integers, sums over replicas (ranks add theirs), no matrix.
 // Included at the end of consensus.hip after affinity.h (quality.h's k_ql_present / k_ql_ids,
-// components.h's cp_graph, affinity.h's k_ia_rank, cluster.h's k_cc_row_slots, k_cc_emit and
-// cc_wave_sum, score.h's segments, fallback entries, SC_D and ScLabT, analysis.h's PhaseMarks and
-// the hipcub wrappers are in scope).
+// components.h's cp_graph, affinity.h's k_ia_rank, cluster.h's cell_chunks, score.h's segments,
+// cell-kernel pieces, fallback plan and ScLabT, analysis.h's PhaseMarks and the hipcub wrappers are
+// in scope).
 //
 // Community graph: cluster ranks as quality.h takes them (presence flags over [0, n) and their
 // scan), one pass over H's canonical edges that appends (rank_lo << 32) | rank_hi with the weight
@@ -19,14 +19,14 @@
 // Pair co-association: every pair gets a LIST side and a WALK side: the larger cluster lists (a on
 // equal sizes), the smaller walks, so the per-pair cost is the smaller size and the list of a
 // cluster is built once for all its partners.  The pairs are sorted by list-side rank; the run
-// lengths are the listed clusters with their partner segments.  Count: k_cc_count's walk, one wave
-// per LISTED cluster, LANES ARE REPLICAS.  Pass 1 builds the lane's (label, count) list in SC_D
+// lengths are the listed clusters with their partner segments.  Count: one wave per LISTED cluster,
+// LANES ARE REPLICAS.  Pass 1 (sc_list_walk) builds the lane's (label, count) list in SC_D
 // registers; pass 2 takes the partners in turn, streams each partner's members, looks the member's
-// label up in the list and adds the count to a 64-bit sum in the lane; one wave reduction and one
-// int64 atomicAdd per (pair, bank) finish the partner.
+// label up in the list (sc_gather4, sc_list_count) and adds the count to a 64-bit sum in the lane;
+// one wave reduction and one int64 atomicAdd per (pair, bank) finish the partner.
 // Fallback: a lane with a ninth label, and every lane of a listed cluster past the length cap, is
-// flagged in ovf[bank * k + cluster] (cluster.h's entries); k_cc_emit's keys are sorted and
-// run-length encoded chunk by chunk, and one thread per (pair, walk member) binary-searches the
+// flagged in ovf[bank * k + cluster] (score.h's entries); cell_chunks sorts and run-length encodes
+// their keys chunk by chunk, and one thread per (pair, walk member) binary-searches the
 // chunk's unique keys for (slot, lab_r(member)) over the flagged lanes.  A slot lies in exactly
 // one chunk, so no cell is split; every path adds integers into the same cell.
 #pragma once
@@ -196,14 +196,14 @@ __global__ __launch_bounds__(256) void k_mc_orient(int64_t np, const uint32_t* _
         lkey[p] = l;
         wrank[p] = w;
     }
-    walk = cc_wave_sum(walk);
+    walk = sc_wave_sum(walk);
     if ((threadIdx.x & 63) == 0 && walk) atomicAdd(&ctr[MC_WALK], walk);
 }
 
 // ------------------------------------------------------------------ count kernel (lanes are replicas)
 // qc[i]: the rank of the i-th listed cluster (k: the pairs of ids that do not occur, skipped); its
 // partners are the pairs qidx[qoff[i] .. qoff[i + 1]), pair p walking the members of cluster
-// wrank[p].  lcap as in k_cc_count, on the list side only: a walk of any length is only read.
+// wrank[p].  lcap: score_list_cap with sum32, on the list side only: a walk of any length is only read.
 // ovf[bank * k + cluster], zeroed by the caller: the lanes left to the fallback.  out[pair] zeroed
 // by the caller.
 __global__ __launch_bounds__(256) void k_mc_count(int64_t nq, const uint32_t* __restrict__ qc,
@@ -226,43 +226,8 @@ __global__ __launch_bounds__(256) void k_mc_count(int64_t nq, const uint32_t* __
         if (len <= lcap) {   // wave-uniform
             int32_t key[SC_D];
             int32_t cnt[SC_D];
-#pragma unroll
-            for (int d = 0; d < SC_D; ++d) { key[d] = -1; cnt[d] = 0; }
             // pass 1: the list of (label, count) of this lane's replica over the listed cluster's members
-            for (int32_t b0 = s0; b0 < s1; b0 += 64) {
-                if (!__any(act && !ov)) break;
-                const int nb = s1 - b0 < 64 ? s1 - b0 : 64;
-                const int32_t myv = b0 + lane < s1 ? sval[b0 + lane] : 0;
-                for (int t = 0; t < nb; t += 4) {
-                    int32_t l[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {   // four rows in flight before the list updates
-                        const int tt = t + j < nb ? t + j : nb - 1;
-                        const int32_t v = __shfl(myv, tt);
-                        l[j] = act ? col[(int64_t)v * ldT] : 0;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (t + j < nb && act && !ov) {
-                            const int32_t lab = l[j];
-                            bool f = false;
-#pragma unroll
-                            for (int d = 0; d < SC_D; ++d) {
-                                const bool h = key[d] == lab;
-                                cnt[d] += h ? 1 : 0;
-                                f |= h;
-                            }
-                            if (!f) {
-                                bool placed = false;
-#pragma unroll
-                                for (int d = 0; d < SC_D; ++d)
-                                    if (!placed && key[d] < 0) { key[d] = lab; cnt[d] = 1; placed = true; }
-                                if (!placed) ov = true;
-                            }
-                        }
-                    }
-                }
-            }
+            sc_list_walk(key, cnt, s0, s1, sval, col, ldT, act, ov, lane);
             const bool live = act && !ov;
             // pass 2: the partners in turn, each partner's members against the lists still in registers
             if (__any(live)) {   // wave-uniform
@@ -281,22 +246,15 @@ __global__ __launch_bounds__(256) void k_mc_count(int64_t nq, const uint32_t* __
                             const int32_t myv = b0 + lane < w1 ? sval[b0 + lane] : 0;
                             for (int t = 0; t < nb; t += 4) {
                                 int32_t l[4];
+                                sc_gather4(l, myv, t, nb, col, ldT, live);
 #pragma unroll
                                 for (int j = 0; j < 4; ++j) {
-                                    const int tt = t + j < nb ? t + j : nb - 1;
-                                    const int32_t v = __shfl(myv, tt);
-                                    l[j] = live ? col[(int64_t)v * ldT] : 0;
-                                }
-#pragma unroll
-                                for (int j = 0; j < 4; ++j) {
-                                    int32_t x = 0;
-#pragma unroll
-                                    for (int d = 0; d < SC_D; ++d) x += key[d] == l[j] ? cnt[d] : 0;
+                                    const int32_t x = sc_list_count(key, cnt, l[j]);
                                     acc += live && t + j < nb ? (unsigned long long)(uint32_t)x : 0ull;
                                 }
                             }
                         }
-                        acc = cc_wave_sum(acc);
+                        acc = sc_wave_sum(acc);
                         if (lane == 0 && acc) atomicAdd(&out[p], acc);
                     }
                 }
@@ -329,7 +287,7 @@ __global__ __launch_bounds__(256) void k_mc_work(int64_t np, int banks, const ui
         }
         work[p] = wk;
     }
-    s = cc_wave_sum(s);
+    s = sc_wave_sum(s);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(&ctr[MC_SLOW], s);
 }
 // One thread per (pair p, member t of its walk side) of the pairs with work (W = the exclusive
@@ -384,7 +342,7 @@ __global__ __launch_bounds__(256) void k_mc_lookup(int64_t n, int64_t np, int ba
         }
         const int64_t p0 = __shfl(p, 0);
         if (__all(p == p0)) {   // wave-uniform
-            sum = cc_wave_sum(sum);
+            sum = sc_wave_sum(sum);
             if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&out[p0], sum);
         } else if (sum)
             atomicAdd(&out[p], sum);
@@ -394,37 +352,21 @@ __global__ __launch_bounds__(256) void k_mc_lookup(int64_t n, int64_t np, int ba
 static int64_t merge_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned long long* ovf, int64_t np,
                               const uint32_t* lrank, const uint32_t* wrank, unsigned long long* ctr,
                               unsigned long long* out) {
-    const int64_t N = c.N, nbk = (int64_t)banks * s.k;
-    int64_t* cnt = ensure<int64_t>(c.sc_e1, nbk + 1);
-    int64_t* E = ensure<int64_t>(c.sc_e2, nbk + 1);
-    k_sc_ovf_keys<<<nblk(nbk + 1), TB, 0, c.stream>>>(nbk, s.k, ovf, s.seg, cnt);
-    exclusive_scan(c, (const int64_t*)cnt, E, nbk + 1);
-    const int64_t T = read_i64(c, E + nbk);
-    if (T == 0) return 0;
-    FC_REQUIRE(nbk * 64 < ((int64_t)1 << 32), FC_ELIMIT, "too many (cluster, replica) slots for the pair co-association fallback");
+    const ScPlan p = score_fallback_plan(c, s, (int64_t)banks * s.k, ovf,
+                                         "too many (cluster, replica) slots for the pair co-association fallback");
+    if (p.T == 0) return 0;
     int64_t* work = ensure<int64_t>(c.mc_work, (size_t)2 * (np + 1));
     int64_t* W = work + (np + 1);
     k_mc_work<<<nblk(np + 1), TB, 0, c.stream>>>(np, banks, lrank, wrank, s.k, ovf, s.seg, work, ctr);
     exclusive_scan(c, (const int64_t*)work, W, np + 1);
     const int64_t threads = read_i64(c, W + np);
     const int64_t slow = read_i64(c, (const int64_t*)(ctr + MC_SLOW));
-    if (threads == 0) return slow;
-    const int64_t cap = std::max<int64_t>(2 * N, c.score_chunk), step = cap - N;
-    unsigned long long* k1 = (unsigned long long*)ensure<uint64_t>(c.sc_fk1, cap);
-    unsigned long long* k2 = (unsigned long long*)ensure<uint64_t>(c.sc_fk2, cap);
-    int32_t* v1 = ensure<int32_t>(c.cc_fv1, cap);   // k_cc_emit's member vertices: not needed here
-    int32_t* rc = ensure<int32_t>(c.sc_fcnt, cap + 1);
-    int32_t* nr = ensure<int32_t>(c.sc_nruns, 4);
-    for (int64_t lo = 0; lo < T; lo += step) {
-        const int64_t hi = lo + step, n = std::min<int64_t>(cap, T - lo);
-        FC_HIP(hipMemsetAsync(k1, 0xff, sizeof(uint64_t) * (size_t)n, c.stream));
-        k_cc_emit<<<std::min<unsigned>(nblk(n), 8192u), TB, 0, c.stream>>>(nbk, s.k, E, ovf, s.seg, s.sval,
-                                                                          c.labT.as<int32_t>(), c.ldT, lo, hi, n, k1, v1);
-        sort_keys_public(c, (const uint64_t*)k1, (uint64_t*)k2, n, 64);
-        run_length(c, (const unsigned long long*)k2, k1, rc, nr, n);
+    if (threads == 0) return slow;   // flagged lists that no pair asks for
+    cell_chunks<false>(c, s, p, ovf, c.labT.as<int32_t>(), c.ldT, [&](const CellChunk& ch) {
         k_mc_lookup<<<std::min<unsigned>(nblk(threads), 8192u), TB, 0, c.stream>>>(
-            threads, np, banks, W, lrank, wrank, s.k, ovf, s.seg, s.sval, c.labT.as<int32_t>(), c.ldT, nr, k1, rc, out);
-    }
+            threads, np, banks, W, lrank, wrank, s.k, ovf, s.seg, s.sval, c.labT.as<int32_t>(), c.ldT, ch.nruns, ch.ukeys,
+            ch.counts, out);
+    });
     return slow;
 }
 
@@ -433,17 +375,12 @@ static int64_t merge_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned 
 void cluster_coassoc(Ctx& c, const int32_t* labels, int64_t np, const int32_t* a, const int32_t* b, int64_t* dev_out,
                      fc_cluster_pair_info* info) {
     score_require(c);
-    const int64_t N = c.N;
     const int banks = (c.n_r + 63) / 64;
     PhaseMarks ph(c, c.mc_ms);
     ph.clear();
     ScLabT lt(c);
     ph.mark();
-    int32_t* in = ensure<int32_t>(c.st_lab, N + 1);
-    FC_HIP(hipMemcpyAsync(in, labels, 4 * (size_t)N, hipMemcpyHostToDevice, c.stream));
-    int32_t* row = ensure<int32_t>(c.cc_row, N);
-    k_cc_row_slots<<<nblk(N), TB, 0, c.stream>>>(N, in, c.tpos.as<int32_t>(), row);
-    const ScSeg s = score_segments(c, (const int32_t*)row);
+    const ScSeg s = partition_segments(c, partition_upload(c, labels));
     // the lists: cluster ids -> ranks, the sides, pair indices by list-side rank
     int32_t* ids = ensure<int32_t>(c.mc_ids, (size_t)2 * np);
     FC_HIP(hipMemcpyAsync(ids, a, 4 * (size_t)np, hipMemcpyHostToDevice, c.stream));
@@ -476,10 +413,9 @@ void cluster_coassoc(Ctx& c, const int32_t* labels, int64_t np, const int32_t* a
     ph.mark();   // pairs
     unsigned long long* ovf = (unsigned long long*)ensure<uint64_t>(c.sc_ovf, (size_t)banks * s.k + 1);
     FC_HIP(hipMemsetAsync(ovf, 0, sizeof(uint64_t) * ((size_t)banks * s.k + 1), c.stream));
-    const int lcap = c.score_slow ? 0 : std::min(c.score_lcap, 1 << 24);
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((nq + 3) / 4, SC_GRID));
-    k_mc_count<<<dim3(gx, banks), TB, 0, c.stream>>>(nq, qc, qoff, idx + np, wrank, s.k, s.seg, s.sval,
-                                                     c.labT.as<int32_t>(), c.ldT, c.n_r, lcap, ovf, out);
+    k_mc_count<<<dim3(score_count_grid(nq), banks), TB, 0, c.stream>>>(nq, qc, qoff, idx + np, wrank, s.k, s.seg, s.sval,
+                                                                      c.labT.as<int32_t>(), c.ldT, c.n_r,
+                                                                      score_list_cap(c, true), ovf, out);
     ph.mark();   // count
     const int64_t slow = merge_fallback(c, s, banks, ovf, np, key, wrank, ctr, out);
     ph.mark();   // fallback

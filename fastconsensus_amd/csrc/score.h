@@ -32,19 +32,26 @@ static void run_length(Ctx& c, const K* in, K* uniq, int32_t* counts, int32_t* n
     FC_HIP(hipcub::DeviceRunLengthEncode::Encode(c.sort_tmp.p, tmp, in, uniq, counts, nruns, (int)n, c.stream));
 }
 
-// ------------------------------------------------------------------ reference labeling
-__global__ void k_sc_ref_slots(int64_t N, const int32_t* in, const int32_t* tpos, int32_t* ref) {
+// ------------------------------------------------------------------ a labeling handed in
+// row[tpos[t]] = in[t]: a labeling in node order as a label row in slot order
+__global__ void k_cc_row_slots(int64_t N, const int32_t* __restrict__ in, const int32_t* __restrict__ tpos,
+                               int32_t* __restrict__ row) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < N) ref[tpos[t]] = in[t];
+    if (t < N) row[tpos[t]] = in[t];
+}
+// labels: host int32[N] in node order -> the context's staging row on the device
+static const int32_t* partition_upload(Ctx& c, const int32_t* labels) {
+    int32_t* in = ensure<int32_t>(c.st_lab, c.N + 1);
+    FC_HIP(hipMemcpyAsync(in, labels, 4 * (size_t)c.N, hipMemcpyHostToDevice, c.stream));
+    return in;
 }
 void score_set_reference(Ctx& c, const int32_t* labels) {
     c.sc_ref_set = false;
     if (!labels) return;
     const int64_t N = c.N;
-    int32_t* in = ensure<int32_t>(c.st_lab, N + 1);
-    FC_HIP(hipMemcpyAsync(in, labels, 4 * (size_t)N, hipMemcpyHostToDevice, c.stream));
+    const int32_t* in = partition_upload(c, labels);
     int32_t* ref = ensure<int32_t>(c.sc_ref, N);
-    k_sc_ref_slots<<<nblk(N), TB, 0, c.stream>>>(N, in, c.tpos.as<int32_t>(), ref);
+    k_cc_row_slots<<<nblk(N), TB, 0, c.stream>>>(N, in, c.tpos.as<int32_t>(), ref);
     sync(c);
     c.sc_ref_set = true;
 }
@@ -86,6 +93,35 @@ static ScSeg score_segments(Ctx& c, const int32_t* row) {
 static ScSeg score_segments(Ctx& c, int idx) {
     return score_segments(c, idx < 0 ? c.sc_ref.as<int32_t>() : c.lab.as<int32_t>() + (int64_t)idx * c.N);
 }
+// in: a partition P on the device in node order (partition_upload's, or the caller's own).
+// Synchronises; sc_ulab / sc_cnt hold P's ascending ids and their sizes until the next row.
+static ScSeg partition_segments(Ctx& c, const int32_t* in) {
+    int32_t* row = ensure<int32_t>(c.cc_row, c.N);
+    k_cc_row_slots<<<nblk(c.N), TB, 0, c.stream>>>(c.N, in, c.tpos.as<int32_t>(), row);
+    return score_segments(c, (const int32_t*)row);
+}
+namespace {
+// ids, sizes, largest size and singletons of partition_segments' clusters, for the calls that report them
+struct PartSummary {
+    std::vector<int32_t> cnt, id;
+    int64_t max_size = 0, singletons = 0;
+    // queues the two copies; the caller synchronises before finish()
+    void fetch(Ctx& c, int64_t k) {
+        cnt.resize((size_t)k);
+        id.resize((size_t)k);
+        FC_HIP(hipMemcpyAsync(cnt.data(), c.sc_cnt.as<int32_t>(), 4 * (size_t)k, hipMemcpyDeviceToHost, c.stream));
+        FC_HIP(hipMemcpyAsync(id.data(), c.sc_ulab.as<int32_t>(), 4 * (size_t)k, hipMemcpyDeviceToHost, c.stream));
+    }
+    void finish(int32_t* ids_out, int64_t* size_out) {
+        for (size_t i = 0; i < cnt.size(); ++i) {
+            max_size = std::max<int64_t>(max_size, cnt[i]);
+            singletons += cnt[i] == 1;
+            if (ids_out) ids_out[i] = id[i];
+            if (size_out) size_out[i] = cnt[i];
+        }
+    }
+};
+}  // namespace
 
 // Per block: sum size^2, max size, sum size ln size and (TOT) the 128-bit sum of (community
 // degree)^2, the community degree from the prefix sums P of kdeg in sorted order.
@@ -167,6 +203,105 @@ static ScStats score_stats(Ctx& c, const ScSeg& s, const Graph* g) {
     return st;
 }
 
+// ------------------------------------------------------------------ the cell kernels' shared pieces
+// Six kernels build the contingency cells C_r[k][d] (the members of segment k that replica r labels
+// d) the same way: one wave per segment, LANES ARE REPLICAS, lane r keeping the distinct labels of its
+// replica with their counts in SC_D registers (k_sc_pairs, k_cc_count, k_vm_count, k_ia_count,
+// k_mc_count, k_cm_match).  What they share is here; what each does with the finished list is its own.
+
+// l[j] = the label this lane's replica (column col of labT) gives member t + j of a batch of nb
+// members, lane i of the wave holding the batch's i-th vertex in myv; the members past the batch
+// repeat its last one, a lane that is not `live` reads nothing.  Four rows in flight.
+__device__ __forceinline__ void sc_gather4(int32_t (&l)[4], int32_t myv, int t, int nb, const int32_t* __restrict__ col,
+                                           int ldT, bool live) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int tt = t + j < nb ? t + j : nb - 1;
+        const int32_t v = __shfl(myv, tt);
+        l[j] = live ? col[(int64_t)v * ldT] : 0;
+    }
+}
+// Builds the lane's (label, count) list over the members sval[s0 .. s1) of one segment.
+// Contract: every lane of the wave calls it with the same s0, s1, sval and ldT (it shuffles).  act:
+// the lane has a replica (col is its column of labT; a lane without one passes any valid column and
+// reads nothing).  ov on entry: the lane is already left to the fallback and only keeps the wave
+// company; on exit it is set as well when the lane met a label with all SC_D slots taken.
+// A lane with act && !ov on exit holds the segment's whole row C_r[k][.]: key[d] >= 0 are its labels,
+// cnt[d] their counts, an unused slot is (-1, 0).  A lane with ov set holds garbage in its list: the
+// walk stops updating it, and stops altogether once no lane of the wave is still building.
+// The scalars come by reference on purpose: by value (noundef) k_cc_count's count phase ran 19 to 33 %
+// longer on the MI355X, by reference it runs as the text written out did (profiles/cell_refactor_ab.txt).
+__device__ __forceinline__ void sc_list_walk(int32_t (&key)[SC_D], int32_t (&cnt)[SC_D], const int32_t& s0,
+                                             const int32_t& s1,
+                                             const int32_t* __restrict__ sval, const int32_t* __restrict__ col, const int& ldT,
+                                             const bool& act, bool& ov, const int& lane) {
+#pragma unroll
+    for (int d = 0; d < SC_D; ++d) { key[d] = -1; cnt[d] = 0; }
+    for (int32_t b0 = s0; b0 < s1; b0 += 64) {
+        if (!__any(act && !ov)) break;
+        const int nb = s1 - b0 < 64 ? s1 - b0 : 64;
+        const int32_t myv = b0 + lane < s1 ? sval[b0 + lane] : 0;
+        for (int t = 0; t < nb; t += 4) {
+            int32_t l[4];
+            sc_gather4(l, myv, t, nb, col, ldT, act);   // before the list updates
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (t + j < nb && act && !ov) {
+                    const int32_t lab = l[j];
+                    bool f = false;
+#pragma unroll
+                    for (int d = 0; d < SC_D; ++d) {
+                        const bool h = key[d] == lab;
+                        cnt[d] += h ? 1 : 0;
+                        f |= h;
+                    }
+                    if (!f) {
+                        bool placed = false;
+#pragma unroll
+                        for (int d = 0; d < SC_D; ++d)
+                            if (!placed && key[d] < 0) { key[d] = lab; cnt[d] = 1; placed = true; }
+                        if (!placed) ov = true;
+                    }
+                }
+            }
+        }
+    }
+}
+// the count of label l in a finished list (0 when the segment has no member of that label)
+__device__ __forceinline__ int32_t sc_list_count(const int32_t (&key)[SC_D], const int32_t (&cnt)[SC_D], int32_t l) {
+    int32_t x = 0;
+#pragma unroll
+    for (int d = 0; d < SC_D; ++d) x += key[d] == l ? cnt[d] : 0;
+    return x;
+}
+__device__ __forceinline__ unsigned long long sc_wave_sum(unsigned long long x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+// Four per-lane values -> their four wave sums in 7 shuffles: the halves of the wave trade two
+// values, the quarters one, and four steps finish inside each group of 16 lanes.  The lanes with
+// (lane & 15) == 0 return the sum of value lane >> 4; the others return partial sums.
+__device__ __forceinline__ unsigned sc_sum4(const unsigned (&c)[4], int lane) {
+    const bool hi = lane & 32, h2 = lane & 16;
+    unsigned a0 = hi ? c[2] : c[0], a1 = hi ? c[3] : c[1];
+    a0 += __shfl_xor(hi ? c[0] : c[2], 32);
+    a1 += __shfl_xor(hi ? c[1] : c[3], 32);
+    unsigned b = h2 ? a1 : a0;
+    b += __shfl_xor(h2 ? a0 : a1, 16);
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) b += __shfl_xor(b, o);
+    return b;
+}
+// lcap of a cell kernel: the longest segment one wave streams, 0 (FC_SCORE_SLOW) sending everything to
+// the fallback.  sum32: the kernel adds a member's counts over the wave in 32 bits (sc_sum4); a count
+// is at most the segment's length, so 64 lanes of a segment of up to 2^24 members stay below 2^32.
+static int score_list_cap(const Ctx& c, bool sum32) {
+    return c.score_slow ? 0 : (sum32 ? std::min(c.score_lcap, 1 << 24) : c.score_lcap);
+}
+// grid x of a cell kernel: blocks of 4 waves over `waves` segments, grid-stride past SC_GRID
+static int score_count_grid(int64_t waves) { return (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, SC_GRID)); }
+
 // ------------------------------------------------------------------ pair kernel (lanes are replicas)
 // want[bank]: the lanes whose pair with this row was asked for.  lcap: longest community one
 // wave streams (0: everything to the fallback).  ovf[bank * k + community]: the lanes left to
@@ -191,42 +326,7 @@ __global__ __launch_bounds__(256) void k_sc_pairs(int64_t k, const int32_t* __re
         if (len <= lcap) {   // wave-uniform
             int32_t key[SC_D];
             int32_t cnt[SC_D];
-#pragma unroll
-            for (int d = 0; d < SC_D; ++d) { key[d] = -1; cnt[d] = 0; }
-            for (int32_t b0 = s0; b0 < s1; b0 += 64) {
-                if (!__any(act && !ov)) break;
-                const int nb = s1 - b0 < 64 ? s1 - b0 : 64;
-                const int32_t myv = b0 + lane < s1 ? sval[b0 + lane] : 0;
-                for (int t = 0; t < nb; t += 4) {
-                    int32_t l[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {   // four rows in flight before the list updates
-                        const int tt = t + j < nb ? t + j : nb - 1;
-                        const int32_t v = __shfl(myv, tt);
-                        l[j] = act ? col[(int64_t)v * ldT] : 0;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (t + j < nb && act && !ov) {
-                            const int32_t lab = l[j];
-                            bool f = false;
-#pragma unroll
-                            for (int d = 0; d < SC_D; ++d) {
-                                const bool h = key[d] == lab;
-                                cnt[d] += h ? 1 : 0;
-                                f |= h;
-                            }
-                            if (!f) {
-                                bool placed = false;
-#pragma unroll
-                                for (int d = 0; d < SC_D; ++d)
-                                    if (!placed && key[d] < 0) { key[d] = lab; cnt[d] = 1; placed = true; }
-                                if (!placed) ov = true;
-                            }
-                        }
-                    }
-                }
-            }
+            sc_list_walk(key, cnt, s0, s1, sval, col, ldT, act, ov, lane);
             if (act && !ov) {
 #pragma unroll
                 for (int d = 0; d < SC_D; ++d)
@@ -383,31 +483,57 @@ __global__ __launch_bounds__(256) void k_sc_fold(const int32_t* __restrict__ nru
         atomicAdd(&acc[3 * LP + t], s_l2[t]);
     }
 }
-static void score_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned long long* ovf, unsigned long long* acc) {
-    const int64_t N = c.N, nbk = (int64_t)banks * s.k;
-    const int LP = banks * 64;
+namespace {
+// the fallback's plan: nbk entries, E their prefix sums, T = E[nbk] keys in all
+struct ScPlan {
+    int64_t nbk = 0, T = 0;
+    const int64_t* E = nullptr;
+};
+// a chunk's buffers: up to cap keys a chunk, one chunk every `step` keys of the stream; k1 takes the
+// emitted keys and then the unique ones, k2 the sorted ones, rc the run lengths, *nr their number
+struct ScChunkBufs {
+    int64_t cap, step;
+    unsigned long long *k1, *k2;
+    int32_t *rc, *nr;
+};
+}  // namespace
+// Counts the entries' keys and scans them; synchronises.  Nothing flagged: T = 0 and the caller is
+// done.  too_many: the caller's message for a partition whose slots do not fit a key's high word.
+static ScPlan score_fallback_plan(Ctx& c, const ScSeg& s, int64_t nbk, const unsigned long long* ovf, const char* too_many) {
     int64_t* cnt = ensure<int64_t>(c.sc_e1, nbk + 1);
     int64_t* E = ensure<int64_t>(c.sc_e2, nbk + 1);
     k_sc_ovf_keys<<<nblk(nbk + 1), TB, 0, c.stream>>>(nbk, s.k, ovf, s.seg, cnt);
     exclusive_scan(c, (const int64_t*)cnt, E, nbk + 1);
     const int64_t T = read_i64(c, E + nbk);
-    if (T == 0) return;
-    FC_REQUIRE(nbk * 64 < ((int64_t)1 << 32), FC_ELIMIT, "too many (community, replica) slots for the scoring fallback");
+    FC_REQUIRE(T == 0 || nbk * 64 < ((int64_t)1 << 32), FC_ELIMIT, too_many);
+    return ScPlan{nbk, T, E};
+}
+static ScChunkBufs score_chunk_buffers(Ctx& c) {
+    ScChunkBufs b;
+    b.cap = std::max<int64_t>(2 * c.N, c.score_chunk);
+    b.step = b.cap - c.N;
+    b.k1 = (unsigned long long*)ensure<uint64_t>(c.sc_fk1, b.cap);
+    b.k2 = (unsigned long long*)ensure<uint64_t>(c.sc_fk2, b.cap);
+    b.rc = ensure<int32_t>(c.sc_fcnt, b.cap + 1);
+    b.nr = ensure<int32_t>(c.sc_nruns, 4);
+    return b;
+}
+static void score_fallback(Ctx& c, const ScSeg& s, int banks, const unsigned long long* ovf, unsigned long long* acc) {
+    const int LP = banks * 64;
+    const ScPlan p = score_fallback_plan(c, s, (int64_t)banks * s.k, ovf,
+                                         "too many (community, replica) slots for the scoring fallback");
+    if (p.T == 0) return;
     FC_REQUIRE((size_t)LP * 32 <= 65536, FC_ELIMIT, "too many replicas for the scoring fallback's LDS table");
-    const int64_t cap = std::max<int64_t>(2 * N, c.score_chunk), step = cap - N;
-    unsigned long long* k1 = (unsigned long long*)ensure<uint64_t>(c.sc_fk1, cap);
-    unsigned long long* k2 = (unsigned long long*)ensure<uint64_t>(c.sc_fk2, cap);
-    int32_t* rc = ensure<int32_t>(c.sc_fcnt, cap);
-    int32_t* nr = ensure<int32_t>(c.sc_nruns, 4);
+    const ScChunkBufs b = score_chunk_buffers(c);
     int64_t* rng = ensure<int64_t>(c.sc_rng, 2);
-    for (int64_t lo = 0; lo < T; lo += step) {
-        const int64_t hi = lo + step, n = std::min<int64_t>(cap, T - lo);
-        FC_HIP(hipMemsetAsync(k1, 0xff, sizeof(uint64_t) * (size_t)n, c.stream));
-        k_sc_chunk_range<<<1, 64, 0, c.stream>>>(nbk, E, lo, hi, rng);
-        k_sc_emit<<<SC_GRID, TB, 0, c.stream>>>(s.k, rng, E, ovf, s.seg, s.sval, c.labT.as<int32_t>(), c.ldT, lo, hi, k1);
-        sort_keys_public(c, (const uint64_t*)k1, (uint64_t*)k2, n, 64);
-        run_length(c, (const unsigned long long*)k2, k1, rc, nr, n);
-        k_sc_fold<<<std::min<unsigned>(nblk(n), 1024u), TB, (size_t)LP * 32, c.stream>>>(nr, k1, rc, s.k, LP, acc);
+    for (int64_t lo = 0; lo < p.T; lo += b.step) {
+        const int64_t hi = lo + b.step, n = std::min<int64_t>(b.cap, p.T - lo);
+        FC_HIP(hipMemsetAsync(b.k1, 0xff, sizeof(uint64_t) * (size_t)n, c.stream));
+        k_sc_chunk_range<<<1, 64, 0, c.stream>>>(p.nbk, p.E, lo, hi, rng);
+        k_sc_emit<<<SC_GRID, TB, 0, c.stream>>>(s.k, rng, p.E, ovf, s.seg, s.sval, c.labT.as<int32_t>(), c.ldT, lo, hi, b.k1);
+        sort_keys_public(c, (const uint64_t*)b.k1, (uint64_t*)b.k2, n, 64);
+        run_length(c, (const unsigned long long*)b.k2, b.k1, b.rc, b.nr, n);
+        k_sc_fold<<<std::min<unsigned>(nblk(n), 1024u), TB, (size_t)LP * 32, c.stream>>>(b.nr, b.k1, b.rc, s.k, LP, acc);
     }
 }
 
@@ -433,7 +559,7 @@ struct ScLabT {
 // every wanted lane of row s against it: out[lane] for lane < n_r
 static void score_row_pairs(Ctx& c, const ScSeg& s, const std::vector<unsigned long long>& want, std::vector<ScLane>& out) {
     const int banks = (c.n_r + 63) / 64, LP = banks * 64;
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((s.k + 3) / 4, SC_GRID));
+    const int gx = score_count_grid(s.k);
     unsigned long long* dwant = (unsigned long long*)ensure<uint64_t>(c.sc_want, banks);
     unsigned long long* hw = (unsigned long long*)(c.hpin + 1024);
     for (int b = 0; b < banks; ++b) hw[b] = want[b];
@@ -442,7 +568,7 @@ static void score_row_pairs(Ctx& c, const ScSeg& s, const std::vector<unsigned l
     unsigned long long* part = (unsigned long long*)ensure<uint64_t>(c.sc_part2, (size_t)banks * gx * 256);
     unsigned long long* res = (unsigned long long*)ensure<uint64_t>(c.sc_res, (size_t)8 * LP);
     FC_HIP(hipMemsetAsync(res + 4 * LP, 0, sizeof(uint64_t) * 4 * LP, c.stream));
-    const int lcap = c.score_slow ? 0 : c.score_lcap;
+    const int lcap = score_list_cap(c, false);
     k_sc_pairs<<<dim3(gx, banks), TB, 0, c.stream>>>(s.k, s.seg, s.sval, c.labT.as<int32_t>(), c.ldT, c.n_r, dwant, lcap,
                                                      ovf, part);
     k_sc_pair_reduce<<<banks, 1024, 0, c.stream>>>(gx, LP, part, res);

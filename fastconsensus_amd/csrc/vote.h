@@ -5,17 +5,18 @@
 //     mapped[r][v] = map_r(lab_r(v))
 //     votes_v(k)   = the replicas r with mapped[r][v] = k;  own[v] = votes_v(P(v))
 //     top[v]       = the cluster of most votes: P(v) when it is among the leaders, else the smallest id
-// Included at the end of consensus.hip after cluster.h (its k_cc_row_slots, k_cc_emit and
-// cc_wave_sum, score.h's segments, SC_D and ScLabT, analysis.h's wave_bin_add are in scope).
+// Included at the end of consensus.hip after cluster.h (its cell_chunks, score.h's segments,
+// cell-kernel pieces, fallback plan and ScLabT, analysis.h's wave_bin_add are in scope).
 //
-// Map: k_cc_count's first pass (one wave per cluster of P, LANES ARE REPLICAS, the (label, count)
+// Map: score.h's sc_list_walk (one wave per cluster of P, LANES ARE REPLICAS, the (label, count)
 // list of the lane's replica in SC_D registers); at the segment's end the list is the row C_r[k][.]
 // and every entry goes to best[lane][label] as one 64-bit atomicMax of
 // (count << 32) | (0xffffffff - rank of the cluster in ascending id order): the maximum is (largest
 // count, smallest id) whatever the order of arrival.  A lane with a ninth label and every lane of a
-// cluster past the length cap go through cluster.h's keys, sorted and run-length encoded: a run is
-// one cell C_r[k][d] and makes the same atomicMax.  One bank of 64 replicas at a time, so `best`
-// is 8 * N * min(n_r, 64) bytes however many replicas the context holds.
+// cluster past the length cap go through cluster.h's cell_chunks: the keys sorted and run-length
+// encoded chunk by chunk, where a run is one cell C_r[k][d] and makes the same atomicMax.  One bank
+// of 64 replicas at a time, so `best` is 8 * N * min(n_r, 64) bytes however many replicas the
+// context holds.
 // Count: one thread per node over mapped[.][t] (coalesced), a register list of VT_D (id, votes);
 // a node with a ninth id is compacted and sorted in LDS by one wave.
 #pragma once
@@ -73,42 +74,7 @@ __global__ __launch_bounds__(256) void k_vm_count(int64_t k, const int32_t* __re
         if (len <= lcap) {   // wave-uniform
             int32_t key[SC_D];
             int32_t cnt[SC_D];
-#pragma unroll
-            for (int d = 0; d < SC_D; ++d) { key[d] = -1; cnt[d] = 0; }
-            for (int32_t b0 = s0; b0 < s1; b0 += 64) {
-                if (!__any(act && !ov)) break;
-                const int nb = s1 - b0 < 64 ? s1 - b0 : 64;
-                const int32_t myv = b0 + lane < s1 ? sval[b0 + lane] : 0;
-                for (int t = 0; t < nb; t += 4) {
-                    int32_t l[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {   // four rows in flight before the list updates
-                        const int tt = t + j < nb ? t + j : nb - 1;
-                        const int32_t v = __shfl(myv, tt);
-                        l[j] = act ? col[(int64_t)v * ldT] : 0;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (t + j < nb && act && !ov) {
-                            const int32_t lab = l[j];
-                            bool f = false;
-#pragma unroll
-                            for (int d = 0; d < SC_D; ++d) {
-                                const bool h = key[d] == lab;
-                                cnt[d] += h ? 1 : 0;
-                                f |= h;
-                            }
-                            if (!f) {
-                                bool placed = false;
-#pragma unroll
-                                for (int d = 0; d < SC_D; ++d)
-                                    if (!placed && key[d] < 0) { key[d] = lab; cnt[d] = 1; placed = true; }
-                                if (!placed) ov = true;
-                            }
-                        }
-                    }
-                }
-            }
+            sc_list_walk(key, cnt, s0, s1, sval, col, ldT, act, ov, lane);
             if (act && !ov) {
                 const unsigned long long low = 0xffffffffull - (unsigned long long)cc;
 #pragma unroll
@@ -120,7 +86,7 @@ __global__ __launch_bounds__(256) void k_vm_count(int64_t k, const int32_t* __re
         const unsigned long long mask = __ballot(ov);
         if (lane == 0) ovf[cc] = mask;
     }
-    fresh = cc_wave_sum(fresh);
+    fresh = sc_wave_sum(fresh);
     if (lane == 0 && fresh) atomicAdd(ncomm, fresh);
 }
 // One run of the sorted fallback keys ((cluster * 64 + lane) << 32 | label) = one cell of `count` members.
@@ -154,33 +120,16 @@ __global__ __launch_bounds__(256) void k_vm_apply(int64_t N, int64_t k, const in
     const uint32_t rank = 0xffffffffu - (uint32_t)best[off + ((uint32_t)d < (uint64_t)N ? d : 0)];
     mapped[off + t] = (int64_t)rank < k ? (int32_t)ulab[rank] : -1;
 }
-// the exact path of one bank; returns the (member, replica) pairs handled here
+// the exact path of one bank (its entries are the clusters: nbk = k); returns the (member, replica)
+// pairs handled here
 static int64_t vote_map_fallback(Ctx& c, const ScSeg& s, const int32_t* labT, const unsigned long long* ovf,
                                  unsigned long long* best, unsigned long long* ncomm) {
-    const int64_t N = c.N, nbk = s.k;
-    int64_t* cnt = ensure<int64_t>(c.sc_e1, nbk + 1);
-    int64_t* E = ensure<int64_t>(c.sc_e2, nbk + 1);
-    k_sc_ovf_keys<<<nblk(nbk + 1), TB, 0, c.stream>>>(nbk, s.k, ovf, s.seg, cnt);
-    exclusive_scan(c, (const int64_t*)cnt, E, nbk + 1);
-    const int64_t T = read_i64(c, E + nbk);
-    if (T == 0) return 0;
-    FC_REQUIRE(nbk * 64 < ((int64_t)1 << 32), FC_ELIMIT, "too many (cluster, replica) slots for the vote map's fallback");
-    const int64_t cap = std::max<int64_t>(2 * N, c.score_chunk), step = cap - N;
-    unsigned long long* k1 = (unsigned long long*)ensure<uint64_t>(c.sc_fk1, cap);
-    unsigned long long* k2 = (unsigned long long*)ensure<uint64_t>(c.sc_fk2, cap);
-    int32_t* v1 = ensure<int32_t>(c.cc_fv1, cap);   // k_cc_emit's member vertices: not needed here
-    int32_t* rc = ensure<int32_t>(c.sc_fcnt, cap + 1);
-    int32_t* nr = ensure<int32_t>(c.sc_nruns, 4);
-    for (int64_t lo = 0; lo < T; lo += step) {
-        const int64_t hi = lo + step, n = std::min<int64_t>(cap, T - lo);
-        FC_HIP(hipMemsetAsync(k1, 0xff, sizeof(uint64_t) * (size_t)n, c.stream));
-        k_cc_emit<<<std::min<unsigned>(nblk(n), 8192u), TB, 0, c.stream>>>(nbk, s.k, E, ovf, s.seg, s.sval, labT, c.ldT, lo,
-                                                                          hi, n, k1, v1);
-        sort_keys_public(c, (const uint64_t*)k1, (uint64_t*)k2, n, 64);
-        run_length(c, (const unsigned long long*)k2, k1, rc, nr, n);
-        k_vm_fold<<<std::min<unsigned>(nblk(n), 4096u), TB, 0, c.stream>>>(nr, k1, rc, N, best, ncomm);
-    }
-    return T;
+    const ScPlan p = score_fallback_plan(c, s, s.k, ovf, "too many (cluster, replica) slots for the vote map's fallback");
+    if (p.T == 0) return 0;
+    cell_chunks<false>(c, s, p, ovf, labT, c.ldT, [&](const CellChunk& ch) {
+        k_vm_fold<<<std::min<unsigned>(nblk(ch.n), 4096u), TB, 0, c.stream>>>(ch.nruns, ch.ukeys, ch.counts, c.N, best, ncomm);
+    });
+    return p.T;
 }
 
 // in: P on the device in node order.  mapped: device int32[n_r][N].  Queues the work; the caller
@@ -189,16 +138,13 @@ static int64_t vote_map_run(Ctx& c, const int32_t* in, int32_t* mapped, int64_t*
     const int64_t N = c.N;
     const int banks = (c.n_r + 63) / 64;
     ph.mark();
-    int32_t* row = ensure<int32_t>(c.cc_row, N);
-    k_cc_row_slots<<<nblk(N), TB, 0, c.stream>>>(N, in, c.tpos.as<int32_t>(), row);
-    const ScSeg s = score_segments(c, (const int32_t*)row);
+    const ScSeg s = partition_segments(c, in);
     ph.mark(0);   // segments
     unsigned long long* best = (unsigned long long*)ensure<uint64_t>(c.vt_best, (size_t)N * std::min(c.n_r, 64));
     unsigned long long* ovf = (unsigned long long*)ensure<uint64_t>(c.sc_ovf, (size_t)s.k + 1);
     unsigned long long* ctr = (unsigned long long*)ensure<uint64_t>(c.vt_ctr, VT_CTRS);
     FC_HIP(hipMemsetAsync(ctr + VT_NCOMM, 0, sizeof(uint64_t), c.stream));
-    const int lcap = c.score_slow ? 0 : std::min(c.score_lcap, 1 << 24);
-    const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((s.k + 3) / 4, SC_GRID));
+    const int lcap = score_list_cap(c, true), gx = score_count_grid(s.k);
     int64_t slow = 0;
     for (int b = 0; b < banks; ++b) {
         const int n_rb = std::min(64, c.n_r - b * 64);
@@ -227,7 +173,7 @@ __global__ __launch_bounds__(256) void k_vc_flags(int64_t n, const int32_t* __re
                                                   unsigned long long* __restrict__ out) {
     unsigned long long s = 0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) s += f[i] != 0;
-    s = cc_wave_sum(s);
+    s = sc_wave_sum(s);
     if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
 }
 // One thread per node t (node order).  A value of mapped that is no id of P sets ctr[VT_BAD] and is
@@ -359,8 +305,8 @@ __global__ __launch_bounds__(64) void k_vc_slow(int64_t N, int nt, int M, const 
             cand = other > cand ? other : cand;
         }
         const int mx = (int)(cand >> 33);
-        const unsigned long long leaders = cc_wave_sum((unsigned long long)(lmax == mx ? lcnt : 0));
-        own = (int)cc_wave_sum((unsigned long long)own);
+        const unsigned long long leaders = sc_wave_sum((unsigned long long)(lmax == mx ? lcnt : 0));
+        own = (int)sc_wave_sum((unsigned long long)own);
         if (lane == 0) {
             const int32_t tid = (int32_t)(0xffffffffu - (uint32_t)cand);
             top[t] = tid; top_votes[t] = mx; own_votes[t] = own;
@@ -425,11 +371,6 @@ static void vote_finish(Ctx& c, bool counted, int nt, int64_t k_map, int64_t slo
     }
     if (info) *info = out;
 }
-static const int32_t* vote_upload(Ctx& c, const int32_t* labels) {
-    int32_t* in = ensure<int32_t>(c.st_lab, c.N + 1);
-    FC_HIP(hipMemcpyAsync(in, labels, 4 * (size_t)c.N, hipMemcpyHostToDevice, c.stream));
-    return in;
-}
 
 // labels: host int32[N] in node order, ids in [0, N), validated by the caller.  All synchronise.
 void vote_map(Ctx& c, const int32_t* labels, int32_t* dev_mapped, fc_vote_info* info) {
@@ -437,13 +378,13 @@ void vote_map(Ctx& c, const int32_t* labels, int32_t* dev_mapped, fc_vote_info* 
     VoteMarks ph(c);
     ScLabT lt(c);
     int64_t k = 0;
-    const int64_t slow = vote_map_run(c, vote_upload(c, labels), dev_mapped, &k, ph);
+    const int64_t slow = vote_map_run(c, partition_upload(c, labels), dev_mapped, &k, ph);
     vote_finish(c, false, c.n_r, k, slow, nullptr, nullptr, nullptr, nullptr, info, ph);
 }
 void vote_count(Ctx& c, const int32_t* labels, const int32_t* dev_mapped, int n_total, int32_t* dev_top, int32_t* dev_tv,
                 int32_t* dev_own, int64_t* own_hist, fc_vote_info* info) {
     VoteMarks ph(c);
-    vote_count_run(c, vote_upload(c, labels), dev_mapped, n_total, ph);
+    vote_count_run(c, partition_upload(c, labels), dev_mapped, n_total, ph);
     vote_finish(c, true, n_total, -1, 0, dev_top, dev_tv, dev_own, own_hist, info, ph);
 }
 void vote(Ctx& c, const int32_t* labels, int32_t* dev_top, int32_t* dev_tv, int32_t* dev_own, int64_t* own_hist,
@@ -452,7 +393,7 @@ void vote(Ctx& c, const int32_t* labels, int32_t* dev_top, int32_t* dev_tv, int3
     VoteMarks ph(c);
     ScLabT lt(c);
     int32_t* mapped = ensure<int32_t>(c.vt_mapped, (size_t)c.n_r * c.N);
-    const int32_t* in = vote_upload(c, labels);
+    const int32_t* in = partition_upload(c, labels);
     int64_t k = 0;
     const int64_t slow = vote_map_run(c, in, mapped, &k, ph);
     vote_count_run(c, in, mapped, c.n_r, ph);
