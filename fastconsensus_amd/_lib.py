@@ -51,7 +51,14 @@ class FastConsensusError(RuntimeError):
         self.code = code
 
 
-class Stats(ctypes.Structure):
+class AsDict:
+    """as_dict() of a ctypes structure: {field: value}, without the alignment field `pad`."""
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
+
+
+class Stats(AsDict, ctypes.Structure):
     _fields_ = [
         ("iterations", ctypes.c_int32), ("exit_check", ctypes.c_int32), ("hit_iter_cap", ctypes.c_int32),
         ("n_p", ctypes.c_int32), ("m_final", ctypes.c_int64), ("partition_edges", ctypes.c_int64),
@@ -63,9 +70,6 @@ class Stats(ctypes.Structure):
         ("lv_heavy_ms", ctypes.c_double), ("lv_heavy_launches", ctypes.c_int64), ("lv_heavy_bytes", ctypes.c_int64),
         ("rl_decide_ms", ctypes.c_double), ("rl_decide_launches", ctypes.c_int64), ("rl_decide_bytes", ctypes.c_int64),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class PartScore(ctypes.Structure):
@@ -86,7 +90,7 @@ class PairScore(ctypes.Structure):
     ]
 
 
-class ConsensusInfo(ctypes.Structure):
+class ConsensusInfo(AsDict, ctypes.Structure):
     """fc_consensus_info"""
     _fields_ = [
         ("edges", ctypes.c_int64), ("kept_edges", ctypes.c_int64), ("unanimous_edges", ctypes.c_int64),
@@ -94,9 +98,6 @@ class ConsensusInfo(ctypes.Structure):
         ("singletons", ctypes.c_int64), ("n_total", ctypes.c_int32), ("passes", ctypes.c_int32),
         ("cut", ctypes.c_double),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class LevelScore(ctypes.Structure):
@@ -108,7 +109,7 @@ class LevelScore(ctypes.Structure):
     ]
 
 
-class ClusterInfo(ctypes.Structure):
+class ClusterInfo(AsDict, ctypes.Structure):
     """fc_cluster_info"""
     _fields_ = [
         ("k", ctypes.c_int64), ("max_size", ctypes.c_int64), ("singletons", ctypes.c_int64),
@@ -116,11 +117,8 @@ class ClusterInfo(ctypes.Structure):
         ("pad", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
-
-class VoteInfo(ctypes.Structure):
+class VoteInfo(AsDict, ctypes.Structure):
     """fc_vote_info"""
     _fields_ = [
         ("k", ctypes.c_int64), ("k_voted", ctypes.c_int64), ("moved", ctypes.c_int64),
@@ -129,33 +127,24 @@ class VoteInfo(ctypes.Structure):
         ("pad", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
-
-class AffinityInfo(ctypes.Structure):
+class AffinityInfo(AsDict, ctypes.Structure):
     """fc_affinity_info"""
     _fields_ = [
         ("k", ctypes.c_int64), ("queried_clusters", ctypes.c_int64), ("slow_lookups", ctypes.c_int64),
         ("n_r", ctypes.c_int32), ("pad", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
-
-class ClusterPairInfo(ctypes.Structure):
+class ClusterPairInfo(AsDict, ctypes.Structure):
     """fc_cluster_pair_info"""
     _fields_ = [
         ("k", ctypes.c_int64), ("listed_clusters", ctypes.c_int64), ("walked_members", ctypes.c_int64),
         ("slow_lookups", ctypes.c_int64), ("n_r", ctypes.c_int32), ("pad", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
-
-class MatchInfo(ctypes.Structure):
+class MatchInfo(AsDict, ctypes.Structure):
     """fc_match_info"""
     _fields_ = [
         ("k", ctypes.c_int64), ("max_size", ctypes.c_int64), ("singletons", ctypes.c_int64),
@@ -163,11 +152,8 @@ class MatchInfo(ctypes.Structure):
         ("n_r", ctypes.c_int32), ("pad", ctypes.c_int32),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad"}
 
-
-class QualityInfo(ctypes.Structure):
+class QualityInfo(AsDict, ctypes.Structure):
     """fc_quality_info"""
     _fields_ = [
         ("k", ctypes.c_int64), ("max_size", ctypes.c_int64), ("singletons", ctypes.c_int64),

@@ -275,18 +275,9 @@ def main(argv=None):
         raise SystemExit("--consensus must lie in [0, 1]")
     if args.consensus is not None and args.consensus_levels:
         raise SystemExit("--consensus and --consensus-levels both write the consensus partition: give one")
-    if args.cluster_consensus and args.consensus is None and not args.consensus_levels:
-        raise SystemExit("--cluster-consensus needs --consensus or --consensus-levels")
-    if args.vote and args.consensus is None and not args.consensus_levels:
-        raise SystemExit("--vote needs --consensus or --consensus-levels")
-    if args.median and args.consensus is None and not args.consensus_levels:
-        raise SystemExit("--median needs --consensus or --consensus-levels")
-    if args.quality and args.consensus is None and not args.consensus_levels:
-        raise SystemExit("--quality needs --consensus or --consensus-levels")
-    if args.merge and args.consensus is None and not args.consensus_levels:
-        raise SystemExit("--merge needs --consensus or --consensus-levels")
-    if args.match and args.consensus is None and not args.consensus_levels:
-        raise SystemExit("--match needs --consensus or --consensus-levels")
+    for flag in ("cluster_consensus", "vote", "median", "quality", "merge", "match"):
+        if getattr(args, flag) and args.consensus is None and not args.consensus_levels:
+            raise SystemExit("--%s needs --consensus or --consensus-levels" % flag.replace("_", "-"))
     cons = ca = cc = vt = md = ql = mg = cm = None
     g = IdGraph.from_edgelist_file(args.f)
     if args.coassoc is not None and not 0 <= args.coassoc <= g.n:

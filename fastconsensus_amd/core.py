@@ -108,8 +108,10 @@ class Engine:
         return ptr(t)
 
     def _written(self):
-        """After a step that wrote a caller device buffer: unless the engine runs on the
-        caller's stream, wait for it, so that torch may read the buffer on its own stream."""
+        """After a native call that wrote a caller device buffer and returned without synchronising
+        its stream (the step calls and fc_consensus_support): unless the engine runs on the caller's
+        stream, wait for it, so that torch may read the buffer on its own.  Every other analysis call
+        synchronises before it returns ("The sync rule") and is followed by none."""
         if not getattr(self, "_shared_stream", False):
             check(self._L.fc_synchronize(self._ctx))
 
@@ -327,11 +329,10 @@ class Engine:
         working graph with its consensus weights): a dict of numpy arrays [n_r] -- k, max_size,
         sum_sq, in_weight (int64), tot_sq (exact Python ints, dtype object), s_log, entropy,
         modularity (float64)."""
-        if graph not in _lib.SCORE_GRAPHS:
-            raise ValueError("graph must be one of %s" % (sorted(_lib.SCORE_GRAPHS),))
+        gid = self._graph_id(graph)
         n_r = self.replica_info()[0]
         rec = np.zeros(max(n_r, 1), dtype=PART_DTYPE)
-        check(self._L.fc_score_partitions(self._ctx, _lib.SCORE_GRAPHS[graph], ptr(rec)))
+        check(self._L.fc_score_partitions(self._ctx, gid, ptr(rec)))
         rec = rec[:n_r]
         out = {k: rec[k].copy() for k in ("k", "max_size", "sum_sq", "in_weight", "s_log", "entropy", "modularity")}
         out["tot_sq"] = np.array([(int(h) << 64) | int(l) for l, h in zip(rec["tot_sq_lo"], rec["tot_sq_hi"])],
@@ -356,9 +357,15 @@ class Engine:
         return rec[:k.value]
 
     # -- the consensus partition (fc_consensus_*) ----------------------------------------
-    def _graph_edges(self, graph):
+    @staticmethod
+    def _graph_id(graph):
+        """The C id (FC_SCORE_GRAPH_*) of "input" / "working"."""
         if graph not in _lib.SCORE_GRAPHS:
             raise ValueError("graph must be one of %s" % (sorted(_lib.SCORE_GRAPHS),))
+        return _lib.SCORE_GRAPHS[graph]
+
+    def _graph_edges(self, graph):
+        self._graph_id(graph)
         _, m, m0 = self.graph_info()
         return m0 if graph == "input" else m
 
@@ -380,17 +387,25 @@ class Engine:
         check(fn(self._ctx, ms))
         return dict(zip(names, ms))
 
-    def _int32_out(self, dev_out, count, contiguous=False):
-        """An int32 device tensor of at least `count` elements: `dev_out` when given (checked), else
-        a new one."""
+    def _flat_out(self, dev_out, count, dtype="int32", name="dev_out", contiguous=True):
+        """A device tensor of `dtype` ("int32" / "int64") with at least `count` elements: `dev_out`
+        when given (checked; `name` is the caller's argument in the message), else a new one."""
         import torch
         if dev_out is None:
-            return torch.empty(max(count, 1), dtype=torch.int32, device="cuda:%d" % self.device)
-        if dev_out.dtype != torch_int32() or dev_out.numel() < count or \
+            return torch.empty(max(count, 1), dtype=getattr(torch, dtype), device="cuda:%d" % self.device)
+        if dev_out.dtype != getattr(torch, dtype) or dev_out.numel() < count or \
                 (contiguous and not dev_out.is_contiguous()):
-            raise ValueError("dev_out must be %s int32 tensor of >= %d elements"
-                             % ("a contiguous" if contiguous else "an", count))
+            raise ValueError("%s must be %s %s tensor of >= %d elements"
+                             % (name, "a contiguous" if contiguous else "an", dtype, count))
         return dev_out
+
+    def _partition(self, labels, ids=True):
+        """The partition `labels` ([n] in node order) with its shape checked: through _node_ids, or
+        (ids=False) as the numpy array it is."""
+        labels = np.asarray(labels)
+        if labels.shape != (self.n,):
+            raise ValueError("the partition must have shape (%d,)" % self.n)
+        return self._node_ids(labels) if ids else labels
 
     def consensus_support(self, graph="input", dev_out=None):
         """Per edge of `graph`, the number of local labelings that put both ends in one community:
@@ -398,9 +413,9 @@ class Engine:
         every engine that loaded the graph with the same seed and options), written into
         `dev_out` when given.  Ranks add theirs (SUM) and hand the total to consensus_partition."""
         m = self._graph_edges(graph)
-        dev_out = self._int32_out(dev_out, m)
-        check(self._L.fc_consensus_support(self._ctx, _lib.SCORE_GRAPHS[graph], self._dev(dev_out)))
-        self._written()
+        dev_out = self._flat_out(dev_out, m, contiguous=False)
+        check(self._L.fc_consensus_support(self._ctx, self._graph_id(graph), self._dev(dev_out)))
+        self._written()   # fc_consensus_support queues the count and returns
         return dev_out[:m]
 
     def consensus_partition(self, agreement=0.5, graph="input", dev_support=None, n_total=None):
@@ -493,7 +508,7 @@ class Engine:
         a = self._node_ids(a)
         b = None if b is None else self._node_ids(b)
         na, nb = len(a), len(a if b is None else b)
-        out = self._int32_out(dev_out, na * nb, contiguous=True)
+        out = self._flat_out(dev_out, na * nb)
         check(self._L.fc_coassociation(self._ctx, na, ptr(a), nb, ptr(b), self._dev(out)))
         return out.reshape(-1)[:na * nb].view(na, nb)
 
@@ -501,7 +516,7 @@ class Engine:
         """Per node pair (pairs[p][0], pairs[p][1]), the number of local labelings that put the
         two in one community: an int32 device tensor [npairs]."""
         pairs = self._node_ids(pairs, 2)
-        out = self._int32_out(dev_out, len(pairs), contiguous=True)
+        out = self._flat_out(dev_out, len(pairs))
         check(self._L.fc_coassoc_pairs(self._ctx, len(pairs), ptr(pairs), self._dev(out)))
         return out.reshape(-1)[:len(pairs)]
 
@@ -521,16 +536,6 @@ class Engine:
         return self._phase_timing(self._L.fc_coassoc_timing, ("ids", "count"))
 
     # -- cluster and item consensus (fc_cluster_consensus) ----------------------------------
-    def _int64_out(self, dev_out, name):
-        """A contiguous int64 device tensor of at least n elements: `dev_out` when given (checked)."""
-        import torch
-        n = self.n
-        if dev_out is None:
-            return torch.empty(max(n, 1), dtype=torch.int64, device="cuda:%d" % self.device)
-        if dev_out.dtype != torch_int64() or dev_out.numel() < n or not dev_out.is_contiguous():
-            raise ValueError("%s must be a contiguous int64 tensor of >= %d elements" % (name, n))
-        return dev_out
-
     def cluster_consensus(self, labels, dev_cluster=None, dev_item=None):
         """Monti et al.'s cluster and item consensus of the partition `labels` ([n] in node order,
         integer ids in [0, n), not necessarily dense: a consensus cut, one of the replicas, a
@@ -545,12 +550,9 @@ class Engine:
         >= n elements to write into (pairs of the K clusters, then zeros; item sums in node
         order); ranks add theirs (SUM), see distributed.cluster_consensus_sharded."""
         n = self.n
-        labels = np.asarray(labels)
-        if labels.shape != (n,):
-            raise ValueError("the partition must have shape (%d,)" % n)
-        lab = self._node_ids(labels)
-        dev_cluster = self._int64_out(dev_cluster, "dev_cluster")
-        dev_item = self._int64_out(dev_item, "dev_item")
+        lab = self._partition(labels)
+        dev_cluster = self._flat_out(dev_cluster, n, "int64", "dev_cluster")
+        dev_item = self._flat_out(dev_item, n, "int64", "dev_item")
         ids = np.empty(max(n, 1), np.int32)
         size = np.empty(max(n, 1), np.int64)
         info = _lib.ClusterInfo()
@@ -571,12 +573,6 @@ class Engine:
         return self._phase_timing(self._L.fc_cluster_consensus_timing, ("segments", "count", "fallback"))
 
     # -- plurality vote (fc_vote_map / fc_vote_count / fc_vote) ----------------------------
-    def _vote_labels(self, labels):
-        labels = np.asarray(labels)
-        if labels.shape != (self.n,):
-            raise ValueError("the partition must have shape (%d,)" % self.n)
-        return self._node_ids(labels)
-
     def vote_map(self, labels, dev_mapped=None):
         """Every local labeling relabelled onto the partition `labels` ([n] in node order, ids in
         [0, n), not necessarily dense): each community of replica r becomes the cluster of
@@ -585,12 +581,11 @@ class Engine:
         `labels`; written into `dev_mapped`, contiguous int32 of >= n_r * n elements, when given)
         and k, mapped_communities, slow_members, n_total (= n_r) of fc_vote_info.  Only this
         depends on which rank holds a replica: distributed.vote_sharded all-gathers it."""
-        lab = self._vote_labels(labels)
+        lab = self._partition(labels)
         n_r, n = self.replica_info()[0], self.n
-        out = self._int32_out(dev_mapped, n_r * n, contiguous=True)
+        out = self._flat_out(dev_mapped, n_r * n)
         info = _lib.VoteInfo()
         check(self._L.fc_vote_map(self._ctx, ptr(lab), self._dev(out), ctypes.addressof(info)))
-        self._written()
         d = info.as_dict()
         res = {k: d[k] for k in ("k", "mapped_communities", "slow_members", "n_total")}
         res["mapped"] = out.reshape(-1)[:n_r * n].view(n_r, n)
@@ -607,7 +602,7 @@ class Engine:
         `dev_mapped`: None (the local labelings are mapped, n_total = their number) or an int32
         device tensor [n_total, n] of vote_map's layout, from this engine or gathered over ranks;
         no labelings are needed then, and the map's three fields are 0."""
-        lab = self._vote_labels(labels)
+        lab = self._partition(labels)
         n = self.n
         if dev_mapped is None:
             nt = self.replica_info()[0]
@@ -615,7 +610,7 @@ class Engine:
             nt = int(dev_mapped.shape[0] if n_total is None else n_total)
             if dev_mapped.dtype != torch_int32() or not dev_mapped.is_contiguous() or dev_mapped.numel() < nt * n:
                 raise ValueError("dev_mapped must be a contiguous int32 tensor of >= n_total * n elements")
-        top, tv, own = (self._int32_out(None, n) for _ in range(3))
+        top, tv, own = (self._flat_out(None, n) for _ in range(3))
         hist = np.zeros(max(nt, 0) + 1, np.int64)
         info = _lib.VoteInfo()
         if dev_mapped is None:
@@ -624,7 +619,6 @@ class Engine:
         else:
             check(self._L.fc_vote_count(self._ctx, ptr(lab), self._dev(dev_mapped), nt, self._dev(top), self._dev(tv),
                                         self._dev(own), ptr(hist), ctypes.addressof(info)))
-        self._written()
         out = info.as_dict()
         out.update(top=top[:n].cpu().numpy(), top_votes=tv[:n].cpu().numpy(), own_votes=own[:n].cpu().numpy(),
                    own_hist=hist)
@@ -647,20 +641,15 @@ class Engine:
         fc_affinity_info fields (k, queried_clusters, slow_lookups, n_r).  `dev_out`: a contiguous
         int64 device tensor of >= npairs elements to write into; ranks add theirs (SUM), see
         distributed.item_affinity_sharded."""
-        import torch
-        lab = self._vote_labels(labels)
+        lab = self._partition(labels)
         nodes, clusters = self._node_ids(nodes), self._node_ids(clusters)
         if len(nodes) != len(clusters):
             raise ValueError("nodes and clusters must have the same length")
         npairs = len(nodes)
-        if dev_out is None:
-            dev_out = torch.empty(max(npairs, 1), dtype=torch.int64, device="cuda:%d" % self.device)
-        elif dev_out.dtype != torch_int64() or dev_out.numel() < npairs or not dev_out.is_contiguous():
-            raise ValueError("dev_out must be a contiguous int64 tensor of >= %d elements" % npairs)
+        dev_out = self._flat_out(dev_out, npairs, "int64")
         info = _lib.AffinityInfo()
         check(self._L.fc_item_affinity(self._ctx, ptr(lab), npairs, ptr(nodes), ptr(clusters), self._dev(dev_out),
                                        ctypes.addressof(info)))
-        self._written()
         out = info.as_dict()
         out["aff"] = dev_out.reshape(-1)[:npairs].cpu().numpy()
         return out
@@ -681,9 +670,7 @@ class Engine:
         few candidate clusters; cluster_consensus gives every node's own-cluster sum in O(n * n_r)."""
         import torch
         nodes = self._node_ids(nodes)
-        labels = np.asarray(labels)
-        if labels.shape != (self.n,):
-            raise ValueError("the partition must have shape (%d,)" % self.n)
+        labels = self._partition(labels, ids=False)
         clusters = np.asarray(clusters).reshape(-1)
         members = [np.flatnonzero(labels == c).astype(np.int32) for c in clusters]
         cols = np.concatenate(members) if members else np.zeros(0, np.int32)
@@ -712,25 +699,21 @@ class Engine:
         singletons, parts, disconnected, in_weight_total, cut_weight, total_degree); and
         conductance, density and modularity_share float64[K], the module-level functions of those
         integers."""
-        if graph not in _lib.SCORE_GRAPHS:
-            raise ValueError("graph must be one of %s" % (sorted(_lib.SCORE_GRAPHS),))
+        gid = self._graph_id(graph)
         n = self.n
-        labels = np.asarray(labels)
-        if labels.shape != (n,):
-            raise ValueError("the partition must have shape (%d,)" % n)
-        lab = self._node_ids(labels)
+        lab = self._partition(labels)
         rec = np.empty(max(n, 1), _lib.COMMUNITY_RECORD)
         nin = np.empty(n, np.int64) if nodes else None
         nout = np.empty(n, np.int64) if nodes else None
         sp = np.empty(n, np.int32) if split else None
         info = _lib.QualityInfo()
-        check(self._L.fc_community_quality(self._ctx, _lib.SCORE_GRAPHS[graph], ptr(lab), ptr(rec), ptr(nin),
-                                           ptr(nout), ptr(sp), ctypes.addressof(info)))
+        check(self._L.fc_community_quality(self._ctx, gid, ptr(lab), ptr(rec), ptr(nin), ptr(nout), ptr(sp),
+                                           ctypes.addressof(info)))
         rec = rec[:info.k]
         out = {("ids" if f == "id" else f): rec[f].copy() for f in rec.dtype.names}
         out["cut"] = out["volume"] - 2 * out["in_weight"]
-        for k, _ in info._fields_:
-            out["in_weight_total" if k == "in_weight" else k] = getattr(info, k)
+        # `in_weight` is the per-cluster array: the info's total takes another name
+        out.update(("in_weight_total" if k == "in_weight" else k, v) for k, v in info.as_dict().items())
         if nodes:
             out.update(node_in=nin, node_out=nout, mixing=mixing(nin, nout))
         if split:
@@ -754,11 +737,11 @@ class Engine:
         at least one edge, ascending by (a, b)), weight int64[npairs] (the sum of w over the joining
         edges), edges int64[npairs] (their number) and npairs."""
         cap = max(self._graph_edges(graph), 1)   # every edge its own pair at the most; the pages stay untouched
-        lab = self._vote_labels(labels)
+        lab = self._partition(labels)
         a, b = np.empty(cap, np.int32), np.empty(cap, np.int32)
         w, e = np.empty(cap, np.int64), np.empty(cap, np.int64)
         cnt = ctypes.c_int64(0)
-        check(self._L.fc_community_graph(self._ctx, _lib.SCORE_GRAPHS[graph], ptr(lab), cap, ptr(a), ptr(b), ptr(w),
+        check(self._L.fc_community_graph(self._ctx, self._graph_id(graph), ptr(lab), cap, ptr(a), ptr(b), ptr(w),
                                          ptr(e), ctypes.byref(cnt)))
         k = cnt.value
         return {"a": a[:k].copy(), "b": b[:k].copy(), "weight": w[:k].copy(), "edges": e[:k].copy(), "npairs": int(k)}
@@ -777,20 +760,15 @@ class Engine:
         fc_cluster_pair_info fields (k, listed_clusters, walked_members, slow_lookups, n_r).
         `dev_out`: a contiguous int64 device tensor of >= npairs elements to write into; ranks add
         theirs (SUM), see distributed.cluster_coassoc_sharded."""
-        import torch
-        lab = self._vote_labels(labels)
+        lab = self._partition(labels)
         a, b = self._node_ids(a), self._node_ids(b)
         if len(a) != len(b):
             raise ValueError("a and b must have the same length")
         npairs = len(a)
-        if dev_out is None:
-            dev_out = torch.empty(max(npairs, 1), dtype=torch.int64, device="cuda:%d" % self.device)
-        elif dev_out.dtype != torch_int64() or dev_out.numel() < npairs or not dev_out.is_contiguous():
-            raise ValueError("dev_out must be a contiguous int64 tensor of >= %d elements" % npairs)
+        dev_out = self._flat_out(dev_out, npairs, "int64")
         info = _lib.ClusterPairInfo()
         check(self._L.fc_cluster_coassoc(self._ctx, ptr(lab), npairs, ptr(a), ptr(b), self._dev(dev_out),
                                          ctypes.addressof(info)))
-        self._written()
         out = info.as_dict()
         out["x"] = dev_out.reshape(-1)[:npairs].cpu().numpy()
         return out
@@ -828,8 +806,8 @@ class Engine:
         J >= 3/4, with J <= 1/2).  `dev_inter` / `dev_csize`: contiguous int32 device tensors
         [>= rows, ld >= K] of one shape to write into (row r's first K entries; the rest is left
         alone); distributed.cluster_match_sharded gathers the ranks' rows."""
-        lab = self._vote_labels(part)
-        oth = None if other is None else self._vote_labels(other)
+        lab = self._partition(part)
+        oth = None if other is None else self._partition(other)
         rows = 1 if other is not None else self.replica_info()[0]
         k = len(np.unique(lab))
         dev_inter = self._match_out(dev_inter, rows, k, "dev_inter")
@@ -960,10 +938,11 @@ def match_summary(inter, size, csize):
             "dissolved": dissolved(inter, size, csize)}
 
 
-def match_result(eng, labels):
+def match_result(eng, labels, cluster_match=None):
     """What fast_consensus(match=True) adds to the `consensus` dict.  The keys carry the call's name:
-    the dict's `stability` is the per-node value of consensus_partition."""
-    cm = eng.cluster_match(labels)
+    the dict's `stability` is the per-node value of consensus_partition.  `cluster_match`: the
+    matching function, labels -> dict (default eng.cluster_match; the sharded driver passes its own)."""
+    cm = (eng.cluster_match if cluster_match is None else cluster_match)(labels)
     return {"match_inter": cm["inter"], "match_csize": cm["csize"], "match_stability": cm["stability"],
             "match_recovered": cm["recovered"], "match_dissolved": cm["dissolved"]}
 
@@ -1027,25 +1006,21 @@ def mixing(node_in, node_out):
 def split_disconnected(eng, labels, graph="input"):
     """`labels` refined to the connected parts of each of its clusters on `graph`, int32[n], the parts
     numbered by their smallest node (Engine.community_quality's `split` alone)."""
-    n = eng.n
-    labels = np.asarray(labels)
-    if labels.shape != (n,):
-        raise ValueError("the partition must have shape (%d,)" % n)
-    if graph not in _lib.SCORE_GRAPHS:
-        raise ValueError("graph must be one of %s" % (sorted(_lib.SCORE_GRAPHS),))
+    labels = eng._partition(labels, ids=False)
+    gid = eng._graph_id(graph)
     lab = eng._node_ids(labels)
-    sp = np.empty(n, np.int32)
-    check(eng._L.fc_community_quality(eng._ctx, _lib.SCORE_GRAPHS[graph], ptr(lab), None, None, None, ptr(sp), None))
+    sp = np.empty(len(lab), np.int32)
+    check(eng._L.fc_community_quality(eng._ctx, gid, ptr(lab), None, None, None, ptr(sp), None))
     return sp
 
 
-def quality_result(eng, cons):
+def quality_result(eng, cons, community_quality=None):
     """What fast_consensus(quality=True) adds to the `consensus` dict: `quality` for its labels and
-    `voted_quality` / `median_quality` for the refinements the same call made."""
-    out = {"quality": eng.community_quality(cons["labels"])}
-    for k in ("voted", "median"):
-        if k in cons:
-            out[k + "_quality"] = eng.community_quality(cons[k])
+    `voted_quality` / `median_quality` for the refinements the same call made.  `community_quality`:
+    labels -> dict (default eng.community_quality)."""
+    cq = eng.community_quality if community_quality is None else community_quality
+    out = {"quality": cq(cons["labels"])}
+    out.update((k + "_quality", cq(cons[k])) for k in ("voted", "median") if k in cons)
     return out
 
 
@@ -1352,6 +1327,51 @@ def merge_start(cons):
         if k in cons:
             return cons[k]
     return cons["labels"]
+
+
+def check_consensus_flags(consensus, **flags):
+    """ValueError for a flag that needs `consensus` and is set without it -- the first of match,
+    merge, quality, median, cluster_consensus, vote among the `flags` given -- then for a
+    `consensus` string other than "best"."""
+    for name in ("match", "merge", "quality", "median", "cluster_consensus", "vote"):
+        if flags.get(name) and consensus is None:
+            raise ValueError('%s=True needs consensus (a threshold or "best")' % name)
+    if isinstance(consensus, str) and consensus != "best":
+        raise ValueError('consensus must be a threshold in [0, 1] or "best"')
+
+
+def refine_consensus(eng, cons, *, vote=False, median=False, quality=False, merge=False, match=False, calls=None):
+    """The optional refinements of the `consensus` dict `cons` in their one order, each adding its
+    *_result keys; returns `cons`.  vote: vote_refine of `labels`.  median: median_refine of `voted`
+    when vote ran, else of `labels`.  quality: quality_result.  merge: merge_refine of
+    merge_start(cons), with quality also `merged_quality`.  match: match_result of `labels`.  All but
+    quality read the labelings, so the chain runs before anything replaces them.
+    calls: {name: callable} in place of the engine's methods vote, cluster_consensus, item_affinity,
+    community_graph, cluster_coassoc, community_quality and cluster_match, and sum_sq (T of the two
+    refinements: a number, or a callable evaluated in front of each).  The sharded driver passes
+    distributed.sharded_calls; with every call given, `eng` is not used."""
+    get = (calls or {}).get
+
+    def total():
+        return get("sum_sq")() if callable(get("sum_sq")) else get("sum_sq")
+
+    if vote:
+        cons.update(vote_result(vote_refine(eng, cons["labels"], vote=get("vote"))))
+    if median:
+        cons.update(median_result(median_refine(
+            eng, cons["voted"] if vote else cons["labels"], vote=get("vote"),
+            cluster_consensus=get("cluster_consensus"), item_affinity=get("item_affinity"), sum_sq=total())))
+    if quality:   # of the graph and the partitions alone: no labelings are read
+        cons.update(quality_result(eng, cons, get("community_quality")))
+    if merge:
+        cons.update(merge_result(merge_refine(
+            eng, merge_start(cons), community_graph=get("community_graph"), cluster_coassoc=get("cluster_coassoc"),
+            cluster_consensus=get("cluster_consensus"), sum_sq=total())))
+        if quality:
+            cons["merged_quality"] = (get("community_quality") or eng.community_quality)(cons["merged"])
+    if match:
+        cons.update(match_result(eng, cons["labels"], get("cluster_match")))
+    return cons
 
 
 def level_of(theta, n_total):
@@ -1864,20 +1884,8 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
     also adds ``truth_match``: the planted communities against the consensus partition (``ids``,
     ``size``, ``inter``, ``csize``, ``jaccard``, ``f1`` per planted community, and ``mean_f1``).
     """
-    if match and consensus is None:
-        raise ValueError("match=True needs consensus (a threshold or \"best\")")
-    if merge and consensus is None:
-        raise ValueError("merge=True needs consensus (a threshold or \"best\")")
-    if quality and consensus is None:
-        raise ValueError("quality=True needs consensus (a threshold or \"best\")")
-    if median and consensus is None:
-        raise ValueError("median=True needs consensus (a threshold or \"best\")")
-    if cluster_consensus and consensus is None:
-        raise ValueError("cluster_consensus=True needs consensus (a threshold or \"best\")")
-    if vote and consensus is None:
-        raise ValueError("vote=True needs consensus (a threshold or \"best\")")
-    if isinstance(consensus, str) and consensus != "best":
-        raise ValueError('consensus must be a threshold in [0, 1] or "best"')
+    check_consensus_flags(consensus, match=match, merge=merge, quality=quality, median=median,
+                          cluster_consensus=cluster_consensus, vote=vote)
     algo = algo_id(algorithm)
     if algo is None:
         return None
@@ -1906,20 +1914,10 @@ def fast_consensus(G, algorithm='louvain', n_p=20, thresh=0.2, delta=0.02, *, se
             cons = eng.consensus_partition(float(consensus)) if consensus is not None else None
         if cluster_consensus:   # before consensus_scores replaces the labelings
             cons.update(cluster_result(eng, cons["labels"]))
-        if vote:   # before consensus_scores replaces the labelings
-            cons.update(vote_result(vote_refine(eng, cons["labels"])))
-        if median:   # before consensus_scores replaces the labelings
-            cons.update(median_result(median_refine(eng, cons["voted"] if vote else cons["labels"])))
-        if quality:   # of the graph and the partitions alone: no labelings are read
-            cons.update(quality_result(eng, cons))
-        if merge:   # last of the refinements; before consensus_scores replaces the labelings
-            cons.update(merge_result(merge_refine(eng, merge_start(cons))))
-            if quality:
-                cons["merged_quality"] = eng.community_quality(cons["merged"])
-        if match:   # before consensus_scores replaces the labelings
-            cons.update(match_result(eng, cons["labels"]))
-            if tr is not None:
-                cons["truth_match"] = truth_match(eng, tr, cons["labels"])
+        if cons is not None:   # before consensus_scores replaces the labelings
+            refine_consensus(eng, cons, vote=vote, median=median, quality=quality, merge=merge, match=match)
+        if match and tr is not None:
+            cons["truth_match"] = truth_match(eng, tr, cons["labels"])
         ca = None
         if coassoc is not None:   # before consensus_scores replaces the labelings
             ca = coassoc_result(eng, coassoc_nodes(g.n, coassoc, g.labels, seed), g.labels, cons)

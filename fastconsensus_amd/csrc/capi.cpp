@@ -112,6 +112,41 @@ template <int N> static int phase_timing(fc_ctx* ctx, double (Ctx::*src)[N], dou
     FC_API_END
 }
 
+// ------------------------------------------------------------------ argument checks
+// Every id of a host array lies in [0, n), else FC_EINVAL naming `prefix`, the id and its index.  `what`
+// names the array where its length or its address is refused; an entry point with checks of its own
+// for those makes them first, in its own order.  Out-of-range ids would be out-of-bounds device
+// accesses (they index [N] tables), so they are refused here, before anything is launched.
+static void check_ids(const Ctx& c, const char* prefix, const int32_t* ids, int64_t count, const char* what = "ids") {
+    FC_REQUIRE(count >= 0, FC_EINVAL, std::string("negative length of ") + what);
+    FC_REQUIRE(ids || count == 0, FC_EINVAL, std::string("null ") + what);
+    const uint32_t lim = (uint32_t)c.N;
+    for (int64_t i = 0; i < count; ++i)
+        FC_REQUIRE((uint32_t)ids[i] < lim, FC_EINVAL,
+                   std::string(prefix) + " " + std::to_string(ids[i]) + " at index " + std::to_string(i) +
+                       " outside [0, n)");
+}
+// the replicas one analysis call handles (the cell kernels' per-lane state)
+static void replica_cap(int count, const char* who, const char* unit = "local replicas") {
+    constexpr int MAX_REPLICAS = 2048;
+    FC_REQUIRE(count <= MAX_REPLICAS, FC_ELIMIT,
+               std::string(who) + " handles at most " + std::to_string(MAX_REPLICAS) + " " + unit);
+}
+static void score_graph(int graph) {
+    FC_REQUIRE(graph == FC_SCORE_GRAPH_INPUT || graph == FC_SCORE_GRAPH_WORKING, FC_EINVAL,
+               "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+}
+// nothing to launch (no queries): the info of an empty call, its cluster count from the host
+template <class Info> static void empty_call_info(const Ctx& c, const int32_t* labels, Info* info) {
+    if (!info) return;
+    std::vector<char> seen((size_t)c.N, 0);
+    int64_t k = 0;
+    for (int64_t i = 0; i < c.N; ++i)
+        if (!seen[labels[i]]) { seen[labels[i]] = 1; ++k; }
+    *info = Info{};
+    info->k = k; info->n_r = c.n_r;
+}
+
 extern "C" {
 
 const char* fc_last_error(void) { return g_err.c_str(); }
@@ -282,13 +317,7 @@ int fc_set_labels(fc_ctx* ctx, int count, const int32_t* labels) {
     FC_API_BEGIN
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
     FC_REQUIRE(count >= 1 && labels, FC_EINVAL, "bad labelings");
-    // community ids index per-replica [N] tables (first-node minima, totals): out-of-range
-    // ids would be out-of-bounds device accesses, so they are refused here
-    const int64_t total = (int64_t)count * c.N;
-    const uint32_t lim = (uint32_t)c.N;
-    for (int64_t i = 0; i < total; ++i)
-        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
-                   "label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    check_ids(c, "label", labels, (int64_t)count * c.N);   // they index per-replica [N] tables
     labels_from_host(c, count, labels);
     c.n_r = count; c.rbase = 0; c.n_p_total = count;
     c.labT_valid = false;
@@ -435,19 +464,14 @@ int fc_score_set_reference(fc_ctx* ctx, const int32_t* labels) {
     FC_CTX(ctx)
     FC_API_BEGIN
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
-    const uint32_t lim = (uint32_t)c.N;
-    if (labels)
-        for (int64_t i = 0; i < c.N; ++i)
-            FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
-                       "reference label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    if (labels) check_ids(c, "reference label", labels, c.N);
     score_set_reference(c, labels);
     FC_API_END
 }
 
-static bool score_graph_id(int graph) { return graph == FC_SCORE_GRAPH_INPUT || graph == FC_SCORE_GRAPH_WORKING; }
 // what fc_consensus_partition and fc_consensus_levels require of the graph id, the support and the state
 static void consensus_input(const Ctx& c, int graph, const void* dev_support, int n_total) {
-    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    score_graph(graph);
     FC_REQUIRE(!dev_support || n_total >= 1, FC_EINVAL, "reduced support needs n_total >= 1");
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
     FC_REQUIRE(dev_support || c.n_r > 0, FC_ESTATE,
@@ -459,7 +483,7 @@ int fc_score_partitions(fc_ctx* ctx, int graph, fc_part_score* out) {
     FC_API_BEGIN
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
     FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings");
-    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    score_graph(graph);
     FC_REQUIRE(out, FC_EINVAL, "null output buffer");
     score_partitions(c, graph, out);
     FC_API_END
@@ -501,7 +525,7 @@ int fc_score_pairs(fc_ctx* ctx, const int32_t* pairs, int64_t* npairs, fc_pair_s
 int fc_consensus_support(fc_ctx* ctx, int graph, void* dev_out) {
     FC_CTX(ctx)
     FC_API_BEGIN
-    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    score_graph(graph);
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
     FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings: run fc_run, fc_cd or fc_set_labels first");
     FC_REQUIRE(dev_out || (graph == FC_SCORE_GRAPH_INPUT ? c.g0.m : c.g.m) == 0, FC_EINVAL, "null output buffer");
@@ -549,22 +573,13 @@ static void coassoc_state(const Ctx& c) {
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
     FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings: run fc_run, fc_cd or fc_set_labels first");
 }
-static void coassoc_ids(const Ctx& c, const char* what, const int32_t* ids, int64_t count) {
-    FC_REQUIRE(count >= 0, FC_EINVAL, std::string("negative length of ") + what);
-    FC_REQUIRE(ids || count == 0, FC_EINVAL, std::string("null ") + what);
-    const uint32_t lim = (uint32_t)c.N;
-    for (int64_t i = 0; i < count; ++i)
-        FC_REQUIRE((uint32_t)ids[i] < lim, FC_EINVAL,
-                   std::string(what) + ": node " + std::to_string(ids[i]) + " at index " + std::to_string(i) +
-                       " outside [0, n)");
-}
 
 int fc_coassociation(fc_ctx* ctx, int64_t na, const int32_t* a, int64_t nb, const int32_t* b, void* dev_out) {
     FC_CTX(ctx)
     FC_API_BEGIN
     coassoc_state(c);
-    coassoc_ids(c, "a", a, na);
-    if (b) coassoc_ids(c, "b", b, nb);
+    check_ids(c, "a: node", a, na, "a");
+    if (b) check_ids(c, "b: node", b, nb, "b");
     const int64_t cols = b ? nb : na;
     FC_REQUIRE(dev_out || na == 0 || cols == 0, FC_EINVAL, "null output buffer");
     coassoc_matrix(c, na, a, nb, b, (int32_t*)dev_out);
@@ -576,7 +591,7 @@ int fc_coassoc_pairs(fc_ctx* ctx, int64_t npairs, const int32_t* pairs, void* de
     FC_API_BEGIN
     coassoc_state(c);
     FC_REQUIRE(npairs >= 0 && npairs < ((int64_t)1 << 40), FC_EINVAL, "bad pair count");
-    coassoc_ids(c, "pairs", pairs, 2 * npairs);
+    check_ids(c, "pairs: node", pairs, 2 * npairs, "pairs");
     FC_REQUIRE(dev_out || npairs == 0, FC_EINVAL, "null output buffer");
     coassoc_pairs(c, npairs, pairs, (int32_t*)dev_out);
     FC_API_END
@@ -586,7 +601,7 @@ int fc_coassoc_hist(fc_ctx* ctx, int64_t k, const int32_t* nodes, int64_t* hist)
     FC_CTX(ctx)
     FC_API_BEGIN
     coassoc_state(c);
-    coassoc_ids(c, "nodes", nodes, k);
+    check_ids(c, "nodes: node", nodes, k, "nodes");
     FC_REQUIRE(hist, FC_EINVAL, "null output buffer");
     coassoc_hist(c, k, nodes, hist);
     FC_API_END
@@ -599,12 +614,9 @@ int fc_cluster_consensus(fc_ctx* ctx, const int32_t* labels, int32_t* ids_out, i
     FC_CTX(ctx)
     FC_API_BEGIN
     coassoc_state(c);
-    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "cluster consensus handles at most 2048 local replicas");
+    replica_cap(c.n_r, "cluster consensus");
     FC_REQUIRE(labels, FC_EINVAL, "null labels");
-    const uint32_t lim = (uint32_t)c.N;
-    for (int64_t i = 0; i < c.N; ++i)
-        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
-                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    check_ids(c, "cluster label", labels, c.N);
     cluster_consensus(c, labels, ids_out, size_out, (int64_t*)dev_cluster, (int64_t*)dev_item, info);
     FC_API_END
 }
@@ -614,17 +626,14 @@ int fc_cluster_consensus_timing(fc_ctx* ctx, double* ms) { return phase_timing(c
 // plurality vote: the partition's ids on the host, before anything is launched
 static void vote_labels(const Ctx& c, const int32_t* labels) {
     FC_REQUIRE(labels, FC_EINVAL, "null labels");
-    const uint32_t lim = (uint32_t)c.N;
-    for (int64_t i = 0; i < c.N; ++i)
-        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
-                   "vote label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    check_ids(c, "vote label", labels, c.N);
 }
 
 int fc_vote_map(fc_ctx* ctx, const int32_t* labels, void* dev_mapped, fc_vote_info* info) {
     FC_CTX(ctx)
     FC_API_BEGIN
     coassoc_state(c);
-    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "the vote handles at most 2048 local replicas");
+    replica_cap(c.n_r, "the vote");
     vote_labels(c, labels);
     FC_REQUIRE(dev_mapped, FC_EINVAL, "null dev_mapped");
     vote_map(c, labels, (int32_t*)dev_mapped, info);
@@ -637,7 +646,7 @@ int fc_vote_count(fc_ctx* ctx, const int32_t* labels, const void* dev_mapped, in
     FC_API_BEGIN
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
     FC_REQUIRE(n_total >= 1, FC_EINVAL, "n_total must be at least 1");
-    FC_REQUIRE(n_total <= 2048, FC_ELIMIT, "the vote handles at most 2048 replicas");
+    replica_cap(n_total, "the vote", "replicas");
     vote_labels(c, labels);
     FC_REQUIRE(dev_mapped, FC_EINVAL, "null dev_mapped");
     vote_count(c, labels, (const int32_t*)dev_mapped, n_total, (int32_t*)dev_top, (int32_t*)dev_top_votes,
@@ -650,7 +659,7 @@ int fc_vote(fc_ctx* ctx, const int32_t* labels, void* dev_top, void* dev_top_vot
     FC_CTX(ctx)
     FC_API_BEGIN
     coassoc_state(c);
-    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "the vote handles at most 2048 local replicas");
+    replica_cap(c.n_r, "the vote");
     vote_labels(c, labels);
     vote(c, labels, (int32_t*)dev_top, (int32_t*)dev_top_votes, (int32_t*)dev_own_votes, own_hist, info);
     FC_API_END
@@ -663,33 +672,19 @@ int fc_item_affinity(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const i
     FC_CTX(ctx)
     FC_API_BEGIN
     coassoc_state(c);
-    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "item affinity handles at most 2048 local replicas");
+    replica_cap(c.n_r, "item affinity");
     FC_REQUIRE(npairs >= 0, FC_EINVAL, "negative query count");
     FC_REQUIRE(npairs < ((int64_t)1 << 31), FC_ELIMIT, "item affinity handles fewer than 2^31 queries a call");
     FC_REQUIRE(labels, FC_EINVAL, "null labels");
     FC_REQUIRE(npairs == 0 || (nodes && clusters), FC_EINVAL, "null query list");
     FC_REQUIRE(npairs == 0 || dev_out, FC_EINVAL, "null output buffer");
-    const uint32_t lim = (uint32_t)c.N;
-    for (int64_t i = 0; i < c.N; ++i)
-        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
-                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
-    for (int64_t p = 0; p < npairs; ++p) {
-        FC_REQUIRE((uint32_t)nodes[p] < lim, FC_EINVAL,
-                   "query node " + std::to_string(nodes[p]) + " at index " + std::to_string(p) + " outside [0, n)");
-        FC_REQUIRE((uint32_t)clusters[p] < lim, FC_EINVAL,
-                   "query cluster " + std::to_string(clusters[p]) + " at index " + std::to_string(p) + " outside [0, n)");
-    }
+    check_ids(c, "cluster label", labels, c.N);
+    check_ids(c, "query node", nodes, npairs);
+    check_ids(c, "query cluster", clusters, npairs);
     for (double& m : c.ia_ms) m = 0.0;
-    if (npairs == 0) {   // nothing to launch: the cluster count from the host
-        if (info) {
-            std::vector<char> seen((size_t)c.N, 0);
-            int64_t k = 0;
-            for (int64_t i = 0; i < c.N; ++i)
-                if (!seen[labels[i]]) { seen[labels[i]] = 1; ++k; }
-            *info = fc_affinity_info{};
-            info->k = k; info->n_r = c.n_r;
-        }
-    } else
+    if (npairs == 0)
+        empty_call_info(c, labels, info);
+    else
         item_affinity(c, labels, npairs, nodes, clusters, (int64_t*)dev_out, info);
     FC_API_END
 }
@@ -701,12 +696,9 @@ int fc_community_quality(fc_ctx* ctx, int graph, const int32_t* labels, fc_commu
     FC_CTX(ctx)
     FC_API_BEGIN
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
-    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    score_graph(graph);
     FC_REQUIRE(labels, FC_EINVAL, "null labels");
-    const uint32_t lim = (uint32_t)c.N;
-    for (int64_t i = 0; i < c.N; ++i)
-        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
-                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    check_ids(c, "cluster label", labels, c.N);
     community_quality(c, graph, labels, out, node_in, node_out, split_out, info);
     FC_API_END
 }
@@ -718,13 +710,10 @@ int fc_community_graph(fc_ctx* ctx, int graph, const int32_t* labels, int64_t ca
     FC_CTX(ctx)
     FC_API_BEGIN
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
-    FC_REQUIRE(score_graph_id(graph), FC_EINVAL, "graph must be FC_SCORE_GRAPH_INPUT or FC_SCORE_GRAPH_WORKING");
+    score_graph(graph);
     FC_REQUIRE(labels, FC_EINVAL, "null labels");
     FC_REQUIRE(npairs_out, FC_EINVAL, "null npairs_out");
-    const uint32_t lim = (uint32_t)c.N;
-    for (int64_t i = 0; i < c.N; ++i)
-        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
-                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
+    check_ids(c, "cluster label", labels, c.N);
     community_graph(c, graph, labels, capacity, (int32_t*)a_out, (int32_t*)b_out, (int64_t*)weight_out,
                     (int64_t*)edges_out, npairs_out);
     FC_API_END
@@ -737,47 +726,24 @@ int fc_cluster_coassoc(fc_ctx* ctx, const int32_t* labels, int64_t npairs, const
     FC_CTX(ctx)
     FC_API_BEGIN
     coassoc_state(c);
-    FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "pair co-association handles at most 2048 local replicas");
+    replica_cap(c.n_r, "pair co-association");
     FC_REQUIRE(npairs >= 0, FC_EINVAL, "negative pair count");
     FC_REQUIRE(npairs < ((int64_t)1 << 31), FC_ELIMIT, "pair co-association handles fewer than 2^31 pairs a call");
     FC_REQUIRE(labels, FC_EINVAL, "null labels");
     FC_REQUIRE(npairs == 0 || (a && b), FC_EINVAL, "null pair list");
     FC_REQUIRE(npairs == 0 || dev_out, FC_EINVAL, "null output buffer");
-    const uint32_t lim = (uint32_t)c.N;
-    for (int64_t i = 0; i < c.N; ++i)
-        FC_REQUIRE((uint32_t)labels[i] < lim, FC_EINVAL,
-                   "cluster label " + std::to_string(labels[i]) + " at index " + std::to_string(i) + " outside [0, n)");
-    for (int64_t p = 0; p < npairs; ++p) {
-        FC_REQUIRE((uint32_t)a[p] < lim, FC_EINVAL,
-                   "pair cluster a " + std::to_string(a[p]) + " at index " + std::to_string(p) + " outside [0, n)");
-        FC_REQUIRE((uint32_t)b[p] < lim, FC_EINVAL,
-                   "pair cluster b " + std::to_string(b[p]) + " at index " + std::to_string(p) + " outside [0, n)");
-    }
+    check_ids(c, "cluster label", labels, c.N);
+    check_ids(c, "pair cluster a", a, npairs);
+    check_ids(c, "pair cluster b", b, npairs);
     for (double& m : c.mc_ms) m = 0.0;
-    if (npairs == 0) {   // nothing to launch: the cluster count from the host
-        if (info) {
-            std::vector<char> seen((size_t)c.N, 0);
-            int64_t k = 0;
-            for (int64_t i = 0; i < c.N; ++i)
-                if (!seen[labels[i]]) { seen[labels[i]] = 1; ++k; }
-            *info = fc_cluster_pair_info{};
-            info->k = k; info->n_r = c.n_r;
-        }
-    } else
+    if (npairs == 0)
+        empty_call_info(c, labels, info);
+    else
         cluster_coassoc(c, labels, npairs, a, b, (int64_t*)dev_out, info);
     FC_API_END
 }
 
 int fc_cluster_coassoc_timing(fc_ctx* ctx, double* ms) { return phase_timing(ctx, &Ctx::mc_ms, ms); }
-
-// cluster match: every id of one host array, before anything is launched
-static void match_ids(const Ctx& c, const char* what, const int32_t* ids) {
-    const uint32_t lim = (uint32_t)c.N;
-    for (int64_t i = 0; i < c.N; ++i)
-        FC_REQUIRE((uint32_t)ids[i] < lim, FC_EINVAL,
-                   std::string(what) + ": id " + std::to_string(ids[i]) + " at index " + std::to_string(i) +
-                       " outside [0, n)");
-}
 
 int fc_cluster_match(fc_ctx* ctx, const int32_t* labels, const int32_t* other, int64_t ld, int32_t* ids_out,
                      int64_t* size_out, void* dev_inter, void* dev_csize, fc_match_info* info) {
@@ -786,11 +752,11 @@ int fc_cluster_match(fc_ctx* ctx, const int32_t* labels, const int32_t* other, i
     FC_REQUIRE(c.N > 0, FC_ESTATE, "no graph loaded");
     if (!other) {
         FC_REQUIRE(c.n_r > 0, FC_ESTATE, "no labelings: run fc_run, fc_cd or fc_set_labels first, or pass `other`");
-        FC_REQUIRE(c.n_r <= 2048, FC_ELIMIT, "the cluster match handles at most 2048 local replicas");
+        replica_cap(c.n_r, "the cluster match");
     }
     FC_REQUIRE(labels, FC_EINVAL, "null labels");
-    match_ids(c, "labels", labels);
-    if (other) match_ids(c, "other", other);
+    check_ids(c, "labels: id", labels, c.N);
+    if (other) check_ids(c, "other: id", other, c.N);
     cluster_match(c, labels, other, ld, ids_out, size_out, (int32_t*)dev_inter, (int32_t*)dev_csize, info);
     FC_API_END
 }

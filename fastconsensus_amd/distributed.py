@@ -28,7 +28,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .core import FINAL_PASS_ITER
+from .core import FINAL_PASS_ITER, check_consensus_flags, refine_consensus
 
 LOUVAIN, LPM, LOUVAIN_NC, LEIDEN, INFOMAP = 0, 1, 2, 3, 4
 
@@ -39,6 +39,49 @@ def on_device(t):
 
 def shard(n_p, rank, world):
     return n_p * rank // world, n_p * (rank + 1) // world
+
+
+def _world():
+    """The number of ranks; 1 without a process group."""
+    return dist.get_world_size() if dist.is_initialized() else 1
+
+
+def _devices(engine, device):
+    """(the engine's device string, the device the collectives run on: the same, or "cpu" for gloo)"""
+    cuda = "cuda:%d" % engine.device
+    return cuda, cuda if str(device).startswith("cuda") else "cpu"
+
+
+def _sum_ranks(*tensors):
+    """One SUM all-reduce per tensor, in place and in argument order, when there are ranks to add;
+    returns the tensors."""
+    if _world() > 1:
+        for t in tensors:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return tensors
+
+
+def _gather_rows(block, sums, comm, axis=0):
+    """All ranks' rows in rank order, and the ranks' counters added.  block: this rank's rows along
+    `axis` (every other extent the same on every rank); sums: its row count, then its further
+    counters.  Two all-gathers: the int64 counters, then the blocks padded along `axis` to the
+    largest (one row at least) on the device `comm`.  Returns (rows on `comm`, summed counters);
+    with one rank no collective is issued and (block, sums) come back as they are."""
+    world = _world()
+    if world <= 1:
+        return block, sums
+    cnt = torch.tensor(sums, dtype=torch.int64, device=comm)
+    cnts = [torch.empty_like(cnt) for _ in range(world)]
+    dist.all_gather(cnts, cnt)
+    cnts = torch.stack(cnts).cpu()
+    shape = list(block.shape)
+    shape[axis] = max(int(cnts[:, 0].max()), 1)
+    buf = torch.zeros(shape, dtype=block.dtype, device=comm)
+    buf.narrow(axis, 0, block.shape[axis]).copy_(block)
+    bufs = [torch.empty_like(buf) for _ in range(world)]
+    dist.all_gather(bufs, buf)
+    rows = torch.cat([bufs[g].narrow(axis, 0, int(cnts[g, 0])) for g in range(world)], dim=axis)
+    return rows, cnts.sum(0).tolist()
 
 
 def _all_reduce_small(t, op, n_p, world, shift):
@@ -102,7 +145,7 @@ class SharedOutput:
         size = max(4 * int(n_p) * int(n), 4)
         name = None
         one_node = True
-        if dist.is_initialized() and dist.get_world_size() > 1:
+        if _world() > 1:
             import socket
             hosts = [None] * dist.get_world_size()
             dist.all_gather_object(hosts, socket.gethostname())
@@ -168,10 +211,7 @@ def coassociation_sharded(engine, a, b=None, device="cuda"):
             mat = mat.cpu()
     else:
         mat = torch.zeros((na, nb), dtype=torch.int32, device=device)
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        mat = mat.contiguous()
-        dist.all_reduce(mat, op=dist.ReduceOp.SUM)
-    return mat
+    return _sum_ranks(mat.contiguous())[0]
 
 
 def coassoc_hist_sharded(engine, nodes, n_total, device="cuda"):
@@ -197,22 +237,14 @@ def cluster_consensus_sharded(engine, labels, n_total, device="cuda"):
     from .core import cluster_consensus, item_consensus
     n = engine.n
     labels = np.asarray(labels)
-    cuda = "cuda:%d" % engine.device
+    cuda, comm = _devices(engine, device)
     pairs = torch.zeros(max(n, 1), dtype=torch.int64, device=cuda)
     item = torch.zeros(max(n, 1), dtype=torch.int64, device=cuda)
     slow = 0
     if engine.replica_info()[0] > 0:
         slow = engine.cluster_consensus(labels, dev_cluster=pairs, dev_item=item)["slow_members"]
     ids, size = np.unique(labels, return_counts=True)
-    slow = torch.tensor([slow], dtype=torch.int64)
-    if not str(device).startswith("cuda"):
-        pairs, item = pairs.cpu(), item.cpu()
-    else:
-        slow = slow.to(cuda)
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(pairs, op=dist.ReduceOp.SUM)
-        dist.all_reduce(item, op=dist.ReduceOp.SUM)
-        dist.all_reduce(slow, op=dist.ReduceOp.SUM)
+    pairs, item, slow = _sum_ranks(pairs.to(comm), item.to(comm), torch.tensor([slow], dtype=torch.int64, device=comm))
     k = len(ids)
     cp, ip = pairs[:k].cpu().numpy(), item[:n].cpu().numpy()
     size = size.astype(np.int64)
@@ -232,26 +264,15 @@ def vote_sharded(engine, labels, n_total, device="cuda"):
     mapped_communities and slow_members summed over the ranks.  A rank without replicas
     contributes no rows; `labels` is the same on every rank."""
     n = engine.n
-    cuda = "cuda:%d" % engine.device
-    comm = cuda if str(device).startswith("cuda") else "cpu"
+    cuda, comm = _devices(engine, device)
     n_r = engine.replica_info()[0]
     mine = torch.empty((0, n), dtype=torch.int32, device=cuda)
     sums = [n_r, 0, 0]
     if n_r > 0:
         m = engine.vote_map(labels)
         mine, sums = m["mapped"], [n_r, m["mapped_communities"], m["slow_members"]]
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        world = dist.get_world_size()
-        cnt = torch.tensor(sums, dtype=torch.int64, device=comm)
-        cnts = [torch.empty_like(cnt) for _ in range(world)]
-        dist.all_gather(cnts, cnt)
-        cnts = torch.stack(cnts).cpu()
-        buf = torch.zeros((max(int(cnts[:, 0].max()), 1), n), dtype=torch.int32, device=comm)
-        buf[:n_r].copy_(mine)
-        bufs = [torch.empty_like(buf) for _ in range(world)]
-        dist.all_gather(bufs, buf)
-        mine = torch.cat([bufs[g][:int(cnts[g, 0])] for g in range(world)]).to(cuda).contiguous()
-        sums = cnts.sum(0).tolist()
+    mine, sums = _gather_rows(mine, sums, comm)
+    mine = mine.to(cuda).contiguous()
     if mine.shape[0] != int(n_total):
         raise ValueError("the ranks hold %d labelings, n_total = %d" % (mine.shape[0], n_total))
     res = engine.vote(labels, dev_mapped=mine, n_total=int(n_total))
@@ -259,22 +280,52 @@ def vote_sharded(engine, labels, n_total, device="cuda"):
     return res
 
 
+def _pair_sums_sharded(engine, method, key, labels, a, b, device):
+    """The body of item_affinity_sharded and cluster_coassoc_sharded.  method: the engine call,
+    (labels, a, b, dev_out=) -> dict with slow_lookups; key: the name of the sums in the result."""
+    cuda, comm = _devices(engine, device)
+    npairs = len(np.asarray(a).reshape(-1))
+    buf = torch.zeros(npairs + 1, dtype=torch.int64, device=cuda)   # the sums, then slow_lookups
+    if engine.replica_info()[0] > 0:
+        buf[npairs] = method(labels, a, b, dev_out=buf)["slow_lookups"]
+    out = _sum_ranks(buf.to(comm))[0].cpu().numpy()
+    return {key: out[:npairs].copy(), "slow_lookups": int(out[npairs])}
+
+
 def item_affinity_sharded(engine, labels, nodes, clusters, device="cuda"):
     """Engine.item_affinity over every rank's replicas: each rank sums over ITS local labelings, one
     int64 SUM all-reduce adds the sums, and every rank returns the same dict: aff int64[npairs] and
     slow_lookups (the ranks' sum).  A rank without replicas contributes zeros; `labels` and the
     query lists are the same on every rank."""
-    cuda = "cuda:%d" % engine.device
-    npairs = len(np.asarray(nodes).reshape(-1))
-    buf = torch.zeros(npairs + 1, dtype=torch.int64, device=cuda)   # the sums, then slow_lookups
+    return _pair_sums_sharded(engine, engine.item_affinity, "aff", labels, nodes, clusters, device)
+
+
+def cluster_coassoc_sharded(engine, labels, a, b, device="cuda"):
+    """Engine.cluster_coassoc over every rank's replicas, as item_affinity_sharded: x int64[npairs]
+    and slow_lookups (the ranks' sum)."""
+    return _pair_sums_sharded(engine, engine.cluster_coassoc, "x", labels, a, b, device)
+
+
+def _sum_sq_sharded(engine, device):
+    """T of core.median_refine / merge_refine: the replicas' sum_sq (score_partitions) added over
+    the ranks, one SUM all-reduce."""
+    t = torch.zeros(1, dtype=torch.int64, device=_devices(engine, device)[1])
     if engine.replica_info()[0] > 0:
-        buf[npairs] = engine.item_affinity(labels, nodes, clusters, dev_out=buf)["slow_lookups"]
-    if not str(device).startswith("cuda"):
-        buf = buf.cpu()
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
-    out = buf.cpu().numpy()
-    return {"aff": out[:npairs].copy(), "slow_lookups": int(out[npairs])}
+        t[0] = int(np.asarray(engine.score_partitions()["sum_sq"], np.int64).sum())
+    return int(_sum_ranks(t)[0].item())
+
+
+def sharded_calls(engine, n_total, device="cuda"):
+    """The `calls` of core.refine_consensus over all n_total replicas of a sharded run: every engine
+    call that reads the labelings through its *_sharded counterpart, and sum_sq as the callable that
+    adds it over the ranks.  What needs no labelings (community_graph, community_quality) stays the
+    engine's own."""
+    return {"vote": lambda lab: vote_sharded(engine, lab, n_total, device),
+            "cluster_consensus": lambda lab: cluster_consensus_sharded(engine, lab, n_total, device),
+            "item_affinity": lambda lab, nd, cl: item_affinity_sharded(engine, lab, nd, cl, device),
+            "cluster_coassoc": lambda lab, a, b: cluster_coassoc_sharded(engine, lab, a, b, device),
+            "cluster_match": lambda lab: cluster_match_sharded(engine, lab, n_total, device),
+            "sum_sq": lambda: _sum_sq_sharded(engine, device)}
 
 
 def median_refine_sharded(engine, labels, n_total, device="cuda", max_rounds=64, candidates=None):
@@ -283,34 +334,10 @@ def median_refine_sharded(engine, labels, n_total, device="cuda", max_rounds=64,
     replicas' sum_sq added over the ranks.  The selection (core.median_moves) is deterministic on
     the same integers, so every rank returns the same dict.  `labels` is the same on every rank."""
     from .core import median_refine
-    t = torch.zeros(1, dtype=torch.int64, device="cuda:%d" % engine.device if str(device).startswith("cuda") else "cpu")
-    if engine.replica_info()[0] > 0:
-        t[0] = int(np.asarray(engine.score_partitions()["sum_sq"], np.int64).sum())
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    return median_refine(engine, labels, max_rounds=max_rounds, candidates=candidates,
-                         vote=lambda lab: vote_sharded(engine, lab, n_total, device),
-                         cluster_consensus=lambda lab: cluster_consensus_sharded(engine, lab, n_total, device),
-                         item_affinity=lambda lab, nd, cl: item_affinity_sharded(engine, lab, nd, cl, device),
-                         sum_sq=int(t.item()))
-
-
-def cluster_coassoc_sharded(engine, labels, a, b, device="cuda"):
-    """Engine.cluster_coassoc over every rank's replicas: each rank sums over ITS local labelings,
-    one int64 SUM all-reduce adds the sums, and every rank returns the same dict: x int64[npairs]
-    and slow_lookups (the ranks' sum).  A rank without replicas contributes zeros; `labels` and the
-    pair lists are the same on every rank."""
-    cuda = "cuda:%d" % engine.device
-    npairs = len(np.asarray(a).reshape(-1))
-    buf = torch.zeros(npairs + 1, dtype=torch.int64, device=cuda)   # the sums, then slow_lookups
-    if engine.replica_info()[0] > 0:
-        buf[npairs] = engine.cluster_coassoc(labels, a, b, dev_out=buf)["slow_lookups"]
-    if not str(device).startswith("cuda"):
-        buf = buf.cpu()
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
-    out = buf.cpu().numpy()
-    return {"x": out[:npairs].copy(), "slow_lookups": int(out[npairs])}
+    c = sharded_calls(engine, n_total, device)
+    return median_refine(engine, labels, max_rounds=max_rounds, candidates=candidates, vote=c["vote"],
+                         cluster_consensus=c["cluster_consensus"], item_affinity=c["item_affinity"],
+                         sum_sq=c["sum_sq"]())
 
 
 def merge_refine_sharded(engine, labels, n_total, device="cuda", graph="input", max_rounds=64, candidates=None):
@@ -320,15 +347,10 @@ def merge_refine_sharded(engine, labels, n_total, device="cuda", graph="input", 
     The selection (core.merge_moves) is deterministic on the same integers, so every rank returns
     the same dict.  `labels` is the same on every rank."""
     from .core import merge_refine
-    t = torch.zeros(1, dtype=torch.int64, device="cuda:%d" % engine.device if str(device).startswith("cuda") else "cpu")
-    if engine.replica_info()[0] > 0:
-        t[0] = int(np.asarray(engine.score_partitions()["sum_sq"], np.int64).sum())
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    c = sharded_calls(engine, n_total, device)
     return merge_refine(engine, labels, graph=graph, max_rounds=max_rounds, candidates=candidates,
-                        cluster_coassoc=lambda lab, a, b: cluster_coassoc_sharded(engine, lab, a, b, device),
-                        cluster_consensus=lambda lab: cluster_consensus_sharded(engine, lab, n_total, device),
-                        sum_sq=int(t.item()))
+                        cluster_coassoc=c["cluster_coassoc"], cluster_consensus=c["cluster_consensus"],
+                        sum_sq=c["sum_sq"]())
 
 
 def cluster_match_sharded(engine, labels, n_total, device="cuda"):
@@ -342,8 +364,7 @@ def cluster_match_sharded(engine, labels, n_total, device="cuda"):
     n_r = n_total.  A rank without replicas contributes no rows; `labels` is the same on every rank."""
     from .core import match_summary
     labels = np.asarray(labels)
-    cuda = "cuda:%d" % engine.device
-    comm = cuda if str(device).startswith("cuda") else "cpu"
+    cuda, comm = _devices(engine, device)
     ids, size = np.unique(labels, return_counts=True)
     k = len(ids)
     n_r = engine.replica_info()[0]
@@ -353,18 +374,7 @@ def cluster_match_sharded(engine, labels, n_total, device="cuda"):
         both = torch.empty((2, n_r, k), dtype=torch.int32, device=cuda)
         cm = engine.cluster_match(labels, dev_inter=both[0], dev_csize=both[1])
         sums = [n_r, cm["perfect"], cm["inter_total"], cm["slow_members"]]
-    if dist.is_initialized() and dist.get_world_size() > 1:
-        world = dist.get_world_size()
-        cnt = torch.tensor(sums, dtype=torch.int64, device=comm)
-        cnts = [torch.empty_like(cnt) for _ in range(world)]
-        dist.all_gather(cnts, cnt)
-        cnts = torch.stack(cnts).cpu()
-        buf = torch.zeros((2, max(int(cnts[:, 0].max()), 1), k), dtype=torch.int32, device=comm)
-        buf[:, :n_r].copy_(both)
-        bufs = [torch.empty_like(buf) for _ in range(world)]
-        dist.all_gather(bufs, buf)
-        both = torch.cat([bufs[g][:, :int(cnts[g, 0])] for g in range(world)], dim=1)
-        sums = cnts.sum(0).tolist()
+    both, sums = _gather_rows(both, sums, comm, axis=1)
     if both.shape[1] != int(n_total):
         raise ValueError("the ranks hold %d labelings, n_total = %d" % (both.shape[1], n_total))
     inter, csize = both[0].cpu().numpy(), both[1].cpu().numpy()
@@ -413,19 +423,8 @@ def run_sharded(engine, algo, n_p, tau, delta, device="cuda", max_iters=1000, ga
     match: (needs consensus) the best match, by Jaccard index, of every consensus community in all
     n_p final partitions (cluster_match_sharded); the dict gains match_inter, match_csize,
     match_stability, match_recovered and match_dissolved, the same on every rank."""
-    if match and consensus is None:
-        raise ValueError("match=True needs consensus (a threshold or \"best\")")
-    if merge and consensus is None:
-        raise ValueError("merge=True needs consensus (a threshold or \"best\")")
-    if quality and consensus is None:
-        raise ValueError("quality=True needs consensus (a threshold or \"best\")")
-    if median and consensus is None:
-        raise ValueError("median=True needs consensus (a threshold or \"best\")")
-    if vote and consensus is None:
-        raise ValueError("vote=True needs consensus (a threshold or \"best\")")
-    if isinstance(consensus, str) and consensus != "best":
-        raise ValueError('consensus must be a threshold in [0, 1] or "best"')
-    world = dist.get_world_size() if dist.is_initialized() else 1
+    check_consensus_flags(consensus, match=match, merge=merge, quality=quality, median=median, vote=vote)
+    world = _world()
     rank = dist.get_rank() if dist.is_initialized() else 0
     if out_shared and world > 1 and out is None:
         # every rank must pass the shared array: a rank without it would take the all-gather
@@ -510,27 +509,8 @@ def _loop(engine, algo, n_p, tau, delta, device, max_iters, gather, world, rank,
     if consensus is not None:
         st["consensus"] = _consensus(engine, consensus if isinstance(consensus, str) else float(consensus), n_p, world,
                                       mine, device)
-        if vote:
-            from .core import vote_refine, vote_result
-            st["consensus"].update(vote_result(vote_refine(
-                engine, st["consensus"]["labels"], vote=lambda lab: vote_sharded(engine, lab, n_p, device))))
-        if median:
-            from .core import median_result
-            start = st["consensus"]["voted" if vote else "labels"]
-            st["consensus"].update(median_result(median_refine_sharded(engine, start, n_p, device)))
-        if quality:
-            from .core import quality_result
-            st["consensus"].update(quality_result(engine, st["consensus"]))
-        if merge:
-            from .core import merge_result, merge_start
-            st["consensus"].update(merge_result(merge_refine_sharded(engine, merge_start(st["consensus"]), n_p, device)))
-            if quality:
-                st["consensus"]["merged_quality"] = engine.community_quality(st["consensus"]["merged"])
-        if match:
-            cm = cluster_match_sharded(engine, st["consensus"]["labels"], n_p, device)
-            st["consensus"].update({"match_inter": cm["inter"], "match_csize": cm["csize"],
-                                    "match_stability": cm["stability"], "match_recovered": cm["recovered"],
-                                    "match_dissolved": cm["dissolved"]})
+        refine_consensus(engine, st["consensus"], vote=vote, median=median, quality=quality, merge=merge, match=match,
+                         calls=sharded_calls(engine, n_p, device))
     if gather and world > 1 and out_shared and out is not None:
         # every rank downloads its rows into the shared host array; the barrier orders the
         # writes before rank 0 hands the array back
