@@ -1,6 +1,7 @@
 """Cluster-wise Jaccard best match on the device (fc_cluster_match) against tests/match_ref.py.
 Everything is an integer: every comparison is np.array_equal, and the derived float arrays (the same
-integers through the same float64 operations) compare with ==."""
+integers through the same float64 operations) compare with ==.  The launch clamps, several chunks at
+the default FC_SCORE_CHUNK and cross products past 2^32 are in tests/test_gpu_match_mid.py."""
 import ctypes
 import os
 
